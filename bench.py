@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: pretrain samples/s of the native fusion-token path, ViT-B / 3 modalities / 256x256 tiles.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
 
 N > 1: one rank per GPU.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N`: RANK / WORLD_SIZE / MASTER_* in the environment), or -- when WORLD_SIZE is absent -- this process starts
@@ -500,6 +500,36 @@ def dp_diagnostics(reducer, world, steps, ranks_dt, device, distributed):
                    "rank_ms_per_step_min": round(min(per_rank), 3), "rank_ms_per_step_max": round(max(per_rank), 3)}}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_PARAM_SAMPLE = 1 << 22         # parameter elements drawn for params.npy (16 MB of float32)
+
+
+def dump_outputs(out_dir, model, losses):
+    """--dump-outputs: what the timed path gave its caller in its LAST step, as DIR/<name>.npy in float32, so that two builds run with
+    the same arguments (same weights, inputs and mask draws) can be compared output for output:
+      <key>.npy   every loss PretrainStep returned (loss, loss_contra, <domain>_loss), shape ()
+      params.npy  the trainable parameters after that step's update, concatenated in named_parameters() order; above
+                  DUMP_PARAM_SAMPLE elements a fixed sample of them: the sorted distinct positions of
+                  numpy.random.default_rng(0).integers(0, total, DUMP_PARAM_SAMPLE)
+    Called after the timed region and before the secondary legs (which continue training the same model)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in losses.items()}
+    params = [p for _, p in model.named_parameters() if p.requires_grad]
+    total = sum(p.numel() for p in params)
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+        if total > DUMP_PARAM_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, total, DUMP_PARAM_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays["params"] = flat.cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(k + ".npy" for k in arrays), "params_total": total,
+            "params_dumped": int(arrays["params"].size)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -545,7 +575,12 @@ def main():
                     "variables onto the implementation switches (tools/tuning_env.py); the default run reads none")
     ap.add_argument("--dry-run", dest="dry_run", action="store_true", help="launcher rehearsal on CPU/gloo (see dry_main)")
     ap.add_argument("--tune-out", default="", help="write the TunableOp table here on exit (to refresh the committed table)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default="", metavar="DIR", help="after the timed steps, write what the "
+                    "last timed step returned (its losses) and the trainable parameters it left (a fixed seeded sample) to DIR/<name>.npy, "
+                    "float32, %d MB at most (see dump_outputs)" % (DUMP_MAX_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config5:
         args.model, args.domains, args.num_encoded_tokens, args.contra = "large", "s1,s2,dem,dnw", 512, "hardneg"
         args.per_sample, args.dropout, args.batch, args.clip_grad = True, True, 64, 1.0
@@ -649,6 +684,7 @@ def main():
     layer_timer, model.layer_timer = model.layer_timer, None
     loss_val = float(losses["loss"])
     assert loss_val == loss_val, "non-finite loss"
+    dumped = dump_outputs(args.dump_outputs, model, losses) if (args.dump_outputs and rank == 0) else None
 
     # ---- secondary legs (same model / optimizer state, continuing the run; never `value`) -----------------------------
     default_doms = args.domains == "s1,s2,dem" and args.fusion_blocks and args.contra == "dino"
@@ -833,6 +869,8 @@ def main():
                            "attention_heads_per_workgroup": hpb, "attention_workgroups": args.batch * (heads // hpb)}
         out.update(dpdiag)
         out.update(leg_out)
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args) if default_doms else None      # the CPU leg is the headline configuration's
         print(json.dumps(out), flush=True)

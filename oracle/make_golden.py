@@ -2,7 +2,8 @@
 
 Run in the build container only (needs /root/reference):
 
-    python oracle/make_golden.py
+    python oracle/make_golden.py            # (re)writes tests/golden/*.npz
+    python oracle/make_golden.py --check    # regenerates into a temporary directory: exit 1 unless byte-for-byte identical
 
 The fixtures are pure data (inputs, weights, expected outputs/gradients, recorded random draws).
 No reference source text is written anywhere.  The committed fixtures are what pins
@@ -668,7 +669,106 @@ def gen_droppath(ref):
     print("droppath.npz:", len(bag), "arrays;", int(kept.numel() - kept.sum()), "of", kept.numel(), "(sample, branch) pairs dropped")
 
 
+# ----------------------------------------------------------------------------------------------
+# tests/test_oracle_vs_reference.py: a configuration the other fixtures do not cover (3 encoder layers of width 16 with 2 heads of 8,
+# 2 decoder layers of width 8 with 2 heads, 32 x 32 tiles in 8 x 8 patches), one training forward + backward of the reference with
+# the harness' losses (MSE / MSE / L1 + 0.3 x DINO), and the reference's generate_random_masks for seeds 0-19 at P = 64, N = 96, B = 2.
+# Stored: what the reference computed and its fixed buffers (zero LayerNorm shifts, sin-cos position tables).  The trainable
+# parameters, the inputs and the masks are drawn by vsref_inputs() from VSREF_SEED, which the test calls with the layout recorded here.
+VSREF_CFG = dict(dim_tokens=16, depth=3, dim_head=8, heads=2, image_size=32, patch_size=8, decoder_dim=8,
+                 decoder_depth=2, decoder_heads=2)
+VSREF_SEED = 21
+VSREF_B, VSREF_N, VSREF_KEEP = 2, 22, (("s1", 7), ("s2", 12), ("dem", 3))
+
+
+def vsref_inputs(layout, cfg=VSREF_CFG, seed=VSREF_SEED):
+    """layout: [(parameter name, shape, 1.0 where the reference initialises it to all ones else 0.0)] of the trainable parameters in
+    state_dict() order -> (params, x, masks).  Each is base + 0.1 N(0, 1) (LayerNorm scales stay near 1), then the tiles N(0, 1), then per
+    domain a mask row with the VSREF_KEEP count of kept patches, shared by the batch -- all from one seeded generator."""
+    g = torch.Generator().manual_seed(seed)
+    params = {k: base + 0.1 * torch.randn(tuple(shape), generator=g) for k, shape, base in layout}
+    size, P = cfg["image_size"], (cfg["image_size"] // cfg["patch_size"]) ** 2
+    x = {d: torch.randn(VSREF_B, c, size, size, generator=g) for d, c in CHANNELS}
+    masks = {}
+    for d, k in VSREF_KEEP:
+        row = torch.ones(P, dtype=torch.long)
+        row[torch.randperm(P, generator=g)[:k]] = 0
+        masks[d] = row[None].repeat(VSREF_B, 1)
+    return params, x, masks
+
+
+def gen_vs_reference(ref):
+    torch.manual_seed(VSREF_SEED)
+    model = ref_loader.build_reference_model(ref, channels=CHANNELS, **VSREF_CFG)
+    sd = model.state_dict()
+    trainable = {n for n, p in model.named_parameters() if p.requires_grad}
+    layout = [(k, list(v.shape), 1.0 if bool((v == 1).all()) else 0.0) for k, v in sd.items() if k in trainable]
+    params, x, masks = vsref_inputs(layout)
+    res = model.load_state_dict(params, strict=False)                     # the buffers keep the reference's own values
+    assert not res.unexpected_keys and set(res.missing_keys) == set(sd) - trainable
+    model.train()
+    ps = VSREF_CFG["patch_size"]
+    out = model(x, task_masks=masks, num_encoded_tokens=VSREF_N)
+    fns = {"s1": ref.cr.MaskedMSELoss(ps, 1), "s2": ref.cr.MaskedMSELoss(ps, 1), "dem": ref.cr.MaskedL1Loss(ps, 1)}
+    tl = {t: fns[t](out[0][t].float(), x[t], mask=masks[t]) for t in out[0]}
+    feats = [c.squeeze() for c in torch.chunk(out[2], 4, dim=1)]
+    lc = sum(ref.cr.dino_loss_func(r.squeeze(), f) for r, f in zip(out[5:], feats))
+    loss = sum(tl.values()) + 0.3 * lc
+    loss.backward()
+    bag = Bag()
+    bag["config"] = np.array(json.dumps(dict(VSREF_CFG, B=VSREF_B, N=VSREF_N)))
+    bag["layout"] = np.array(json.dumps(layout))
+    for k, v in sd.items():
+        if k not in trainable:
+            bag["buffer/" + k] = npy(v)
+    for d in x:
+        bag["pred/" + d] = npy(out[0][d])
+    for i in (2, 3, 4, 5, 6, 7):
+        bag["out/%d" % i] = npy(out[i])
+    bag["loss"] = npy(loss)
+    # gradients: one flat array, the parameters that have one concatenated in named_parameters() order (grad_names)
+    named = list(model.named_parameters())
+    bag["grad_names"] = np.array(json.dumps([n for n, p in named if p.grad is not None]))
+    bag["grads"] = npy(torch.cat([p.grad.reshape(-1) for _, p in named if p.grad is not None]))
+    bag["no_grad"] = np.array(json.dumps([n for n, p in named if p.grad is None]))
+
+    draws_model = ref_loader.build_reference_model(ref, dim_tokens=32, depth=1, dim_head=32, heads=1, image_size=128,
+                                                   decoder_dim=32, decoder_depth=1, decoder_heads=1)
+    P, N, B = 64, 96, 2
+    draws = []
+    for seed in range(20):                            # row `seed` of each draws/ array: torch.manual_seed(seed)
+        toks = {d: torch.zeros(B, P, 4) for d, _ in CHANNELS}
+        torch.manual_seed(seed)
+        tm, ids_keep, ids_restore = draws_model.generate_random_masks(toks, N, alphas=1.0)
+        draws.append((torch.cat([tm[d] for d, _ in CHANNELS], 1), ids_keep, ids_restore))
+    for i, name in enumerate(("task_mask", "ids_keep", "ids_restore")):
+        bag["draws/" + name] = npy(torch.stack([d[i] for d in draws]).to(torch.int16))
+    bag["draws_shape"] = np.array([P, N, B])
+    np.savez_compressed(os.path.join(OUT, "vs_reference.npz"), **bag)
+    print("vs_reference.npz:", len(bag), "arrays")
+
+
+def check_against(committed, fresh):
+    """Every committed fixture regenerated byte for byte (the generators seed the RNG before every module construction)."""
+    bad = []
+    for f in sorted(os.listdir(committed)):
+        if not f.endswith(".npz"):
+            continue
+        a, b = np.load(os.path.join(committed, f)), np.load(os.path.join(fresh, f))
+        if sorted(a.files) != sorted(b.files):
+            bad.append(f)
+            continue
+        bad += ["%s:%s" % (f, k) for k in a.files if not np.array_equal(a[k], b[k], equal_nan=a[k].dtype.kind == "f")]
+    print("regenerated fixtures:", "identical" if not bad else "DIFFER: " + ", ".join(bad))
+    return not bad
+
+
 if __name__ == "__main__":
+    check = "--check" in sys.argv[1:]           # regenerate into a temporary directory and compare with the committed files
+    if check:
+        import shutil
+        import tempfile
+        committed, OUT = OUT, tempfile.mkdtemp(prefix="mmae_golden_")
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(1)          # single-threaded reductions: the fixtures regenerate byte for byte
     ref = ref_loader.load()
@@ -679,5 +779,10 @@ if __name__ == "__main__":
     gen_aux()
     gen_quad()
     gen_droppath(ref)
+    gen_vs_reference(ref)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
+    if check:
+        ok = check_against(committed, OUT)
+        shutil.rmtree(OUT, ignore_errors=True)
+        sys.exit(0 if ok else 1)

@@ -2,8 +2,7 @@
 
 Only usable in the build container, where the read-only reference checkout lives at
 /root/reference.  It is used by `oracle/make_golden.py` to generate the committed fixtures in
-`tests/golden/` and by `tests/test_oracle_vs_reference.py` (skipped when the checkout is absent,
-e.g. on the GPU box).  Nothing in the product package imports this file.
+`tests/golden/`; no test imports it.  Nothing in the product package imports this file.
 
 Why a custom loader:
   * pretraining/multimae/__init__.py imports .multimae -> .zorro_utils, and
