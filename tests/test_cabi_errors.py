@@ -42,6 +42,37 @@ def test_attention_argument_checks():
     assert fwd(rows=0) == -1
 
 
+def test_modattn_argument_checks():
+    l = _lib.lib()
+    buf = (ctypes.c_char * 4096)()
+    a16 = (ctypes.addressof(buf) + 15) // 16 * 16
+    P = ctypes.c_void_p
+
+    # every call below breaks exactly one rule; all other arguments are valid (a call with none broken would launch)
+    def fwd(dtype=1, dh=64, B=2, Pn=4, ns=4, I=512, q=a16, kv=a16, out=a16, qs=512, kvs=1024, os_=512):
+        return l.mmae_modattn_fwd(dtype, dh, B, Pn, ns, I, P(q), qs, P(kv), kvs, P(a16), P(out), os_, 0.125, None)
+
+    def bwd(dtype=1, dh=64, B=2, Pn=4, ns=4, I=512, q=a16, kv=a16, dout=a16, dq=a16, dkv=a16, qs=512, kvs=1024, dos=512,
+            dqs=512, dkvs=1024, shared_base=0):
+        return l.mmae_modattn_bwd(dtype, dh, B, Pn, ns, I, P(q), qs, P(kv), kvs, P(a16), P(dout), dos, P(dq), dqs, P(dkv),
+                                  dkvs, shared_base, 0.125, P(a16), None)
+    for f in (fwd, bwd):
+        assert f(ns=0) == -1 and f(ns=9) == -1              # 1 <= M+1 <= 8 slots
+        assert f(I=1040) == -1 and f(I=1056, dh=32) == -1 and f(I=1088, dh=64) == -1   # at most two 512-column chunks
+        assert f(I=520) == -1 and f(I=528, dh=64) == -1     # inner a multiple of head_dim
+        assert f(dh=48, I=480) == -1                        # head_dim 32 / 64 only
+        assert f(dtype=7) == -1                             # fp32 / bf16 only
+        assert f(B=0) == -1 and f(Pn=0) == -1 and f(I=0) == -1
+        assert f(qs=516) == -1 and f(kvs=1028) == -1        # row strides in multiples of 8 elements
+        assert f(q=a16 + 2) == -1 and f(kv=a16 + 8) == -1   # operands 16-byte aligned
+    assert fwd(os_=1020) == -1 and fwd(out=a16 + 4) == -1
+    assert bwd(dos=508) == -1 and bwd(dqs=4) == -1 and bwd(dkvs=1030) == -1
+    assert bwd(dout=a16 + 4) == -1 and bwd(dq=a16 + 2) == -1 and bwd(dkv=a16 + 8) == -1
+    assert bwd(shared_base=-1) == -1
+    assert l.mmae_modattn_bwd_nsplit(1) == 1 and l.mmae_modattn_bwd_nsplit(64) == 2
+    assert l.mmae_modattn_bwd_nsplit(256) == 8 and l.mmae_modattn_bwd_nsplit(600) == 16
+
+
 def test_row_kernel_argument_checks():
     l = _lib.lib()
     buf = (ctypes.c_char * 4096)()
