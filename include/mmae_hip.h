@@ -27,7 +27,7 @@ extern "C" {
                                 mmae_mha_bwd_ws_floats, mmae_gemm_nt, mmae_gemm_geglu, mmae_gemm_tn, mmae_splitk_sum_multi.  5: the optimizer control block grew
                                 from 4 to 8 floats (mmae_adamw_control / _step_ctl read [4], [5]); + mmae_adamw_tick, mmae_mha_fwd_route.  6: + mmae_pad_copy_bf16_batched
                                 (additive: no existing signature changed).  7: + mmae_mha_bwd_fused, mmae_mha_bwd_fused_supported, mmae_mha_bwd_fused_ws_floats
-                                (additive) */
+                                (additive); later additive entry points keep 7: mmae_trunc_standardize */
 int mmae_abi_version(void);
 /* hipError_t of this thread's most recent launch that returned MMAE_ERR_LAUNCH (0: none); reading resets it. */
 int mmae_last_hip_error(void);
@@ -260,6 +260,14 @@ int mmae_grad_norm(long n, const float* g, float* partial_ws_2048, float* out_no
 #define MMAE_RAW_U8 1
 int mmae_stage_tiles(int kind, int in_dtype, int B, int C, int H, int W, int factor, const void* raw, float* out,
                      const float* mean, const float* stdv, void* stream);
+
+/* ---- truncated depth standardisation (PT/pretrain_mmae.py:452-458, --standardize_depth; PT/pretrain_mmae_my.py:468-474) ---------
+ * x, y: (B, n) fp32, n = C*H*W of one DSM tile.  Per sample: the values at sorted ranks [k_lo, k_hi) -- the host passes exactly
+ * int(0.1 * n) / int(0.9 * n) -- give mean and unbiased variance var (torch.var, correction 1); y = (x - mean) / sqrt(var + eps).
+ * Exact order statistics (radix select, NaN ranked above +inf as torch.sort does), no sort, no workspace; bitwise reproducible.
+ * mean / stdv: (B) fp32 outputs of mean and sqrt(var + eps), or NULL.  n < 2^31; k_lo >= 0, k_hi <= n, k_hi - k_lo >= 2. */
+int mmae_trunc_standardize(int B, long n, long k_lo, long k_hi, float eps, const float* x, float* y, float* mean, float* stdv,
+                           void* stream);
 
 /* ---- mask bookkeeping (MM/multimae_crossattn.py:233-272 with injected draws; :402-447, :454-462, :489-493) ---------- */
 int mmae_masks_from_draws(int R, int M, int P, int N, const float* dirichlet, const float* noise,

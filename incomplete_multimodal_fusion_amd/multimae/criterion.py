@@ -4,6 +4,8 @@
 Differences that are deliberate and documented in DESIGN.md:
   * an all-zero mask returns a float32 zero (the reference returns an int64 `tensor(0)`, criterion.py:101-102);
   * a sample whose mask row is empty gets a zero gradient (the reference's 0/0 gives NaN gradients there).
+  * the truncated depth standardisation (ops.trunc_standardize, pretrain_mmae.py:452-458) raises ValueError when its slice holds
+    fewer than two values (the reference's var gives NaN there).
 """
 import torch
 import torch.nn as nn

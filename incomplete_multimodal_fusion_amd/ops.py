@@ -1522,6 +1522,37 @@ def hardneg_loss(o1, o2, tau_plus=0.1, beta=1.0, temperature=0.5):
     return _HardNeg.apply(o1, o2, tau_plus, beta, temperature)
 
 
+# ------------------------------------------------------------------------------------------------ depth standardisation
+def trunc_standardize(x: torch.Tensor, lo: float = 0.1, hi: float = 0.9, eps: float = 1e-6, return_stats: bool = False):
+    """Truncated per-sample standardisation of the DSM (pretrain_mmae.py:452-458, --standardize_depth): the values at sorted
+    ranks [int(lo n), int(hi n)) of each sample's n = C*H*W values give mean and unbiased variance; the whole sample becomes
+    (x - mean) / sqrt(var + eps).  x: (B, C, H, W) or (B, n) fp32 on the device.  Returns a new tensor of x's shape (x is left as
+    it was), or (y, mean, std) with return_stats, mean / std (B,) fp32, std = sqrt(var + eps).  Not differentiable: it prepares
+    the input and the reconstruction target of the dem task.
+    Deviation (criterion.py / DESIGN.md): a slice of fewer than 2 values, where the reference's var gives NaN, is a ValueError."""
+    if not x.is_cuda:
+        raise _lib.MmaeLibraryError("mmae HIP kernels need device tensors (got %s); there is no CPU path" % x.device)
+    if x.dtype != torch.float32:
+        raise ValueError("trunc_standardize: fp32 input expected (got %s)" % x.dtype)
+    if x.dim() not in (2, 4):
+        raise ValueError("trunc_standardize: (B, C, H, W) or (B, n) expected (got shape %s)" % (tuple(x.shape),))
+    B = x.shape[0]
+    n = 1
+    for s in x.shape[1:]:
+        n *= int(s)
+    k_lo, k_hi = int(lo * n), int(hi * n)                  # exactly the reference's slice bounds, computed on the host
+    if k_hi - k_lo < 2:
+        raise ValueError("trunc_standardize: the slice [%d, %d) of %d values per sample holds fewer than 2 (the reference's "
+                         "variance would be NaN)" % (k_lo, k_hi, n))
+    xc = _c(x)
+    y = torch.empty_like(xc)
+    mean = torch.empty(B, dtype=torch.float32, device=x.device) if return_stats else None
+    std = torch.empty(B, dtype=torch.float32, device=x.device) if return_stats else None
+    if B:
+        call("mmae_trunc_standardize", B, n, k_lo, k_hi, float(eps), ptr(xc), ptr(y), ptr(mean), ptr(std), stream())
+    return (y, mean, std) if return_stats else y
+
+
 # ------------------------------------------------------------------------------------------------ mask bookkeeping
 def masks_from_draws(dirichlet, noise, noise_all, N: int):
     """dirichlet (R,M) f32, noise (R,M,P) f32, noise_all (R,M*P) f32 on device ->

@@ -147,8 +147,9 @@ def cosine_scheduler(base_value, final_value, epochs, niter_per_ep, warmup_epoch
 
 def step_losses(out, tasks_dict: Dict[str, torch.Tensor], masks: Dict[str, torch.Tensor], patch_size: int = 16,
                 loss_fns=None, contra_weight: Optional[float] = None, contra: str = 'dino', loss_balancer=None,
-                contra_loss=None):
+                contra_loss=None, loss_on_unmasked: bool = False):
     """pretrain_mmae.py:479-500 with NoWeightingStrategy (utils/task_balancing.py:11-19) by default.
+    loss_on_unmasked: every task loss over all patches, mask=None (--loss_on_unmasked, pretrain_mmae.py:110-111, :482-486).
     contra='dino': sum_m dino_loss_func(return_token_m, pooled_m), weight 0.3 (pretrain_mmae.py:493,:500);
     contra='hardneg': HardNegtive_loss over every pair of the pooled return tokens (modalities + fusion), weight 1
     (pretrain_mmae_s2dsm.py:482-492 written for M modalities);
@@ -162,10 +163,11 @@ def step_losses(out, tasks_dict: Dict[str, torch.Tensor], masks: Dict[str, torch
     for task in preds:
         pred = preds[task].float()
         fn = loss_fns[task]
+        mask = None if loss_on_unmasked else masks.get(task, None)
         if isinstance(pred, mc.PredTokens):
-            task_losses[task] = fn.forward_tokens(pred.tokens, tasks_dict[task], mask=masks.get(task, None))
+            task_losses[task] = fn.forward_tokens(pred.tokens, tasks_dict[task], mask=mask)
         else:
-            task_losses[task] = fn(pred, tasks_dict[task], mask=masks.get(task, None))
+            task_losses[task] = fn(pred, tasks_dict[task], mask=mask)
     feats = [f.squeeze(1) for f in torch.chunk(pooled, pooled.shape[1], dim=1)]   # :489-490 (squeeze the token axis)
     if contra == 'none':
         loss_contra, w = torch.zeros((), device=pooled.device), 0.0
@@ -183,19 +185,34 @@ def step_losses(out, tasks_dict: Dict[str, torch.Tensor], masks: Dict[str, torch
     return task_losses, loss_contra, loss
 
 
+def standardize_depth(tasks_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Truncated depth standardisation of the batch (pretrain_mmae.py:452-458, --standardize_depth; pretrain_mmae_my.py:468-474):
+    a new dict whose 'dem' (when present) is standardised per sample by the mean / unbiased variance of its values between the
+    10 % and 90 % ranks (ops.trunc_standardize, no sort); every other entry, and the caller's tensors, as they were."""
+    out = dict(tasks_dict)
+    if 'dem' in out:
+        out['dem'] = ops.trunc_standardize(out['dem'])
+    return out
+
+
 class PretrainStep:
     """One optimizer step on a batch of tiles already resident on the device.  No host synchronisation.
 
     clip_grad / skip_grad: NativeScaler's options (utils/native_scaler.py:20-40; the driver passes max_norm /
     max_skip_norm, pretrain_mmae.py:510-513).  With the flat engine they -- and the non-finite-gradient guard torch's
     GradScaler provides for the reference -- are evaluated on the device (engine.FlatAdamW.step); with a torch optimizer
-    clip_grad uses torch.nn.utils.clip_grad_norm_ and skip_grad costs one host sync."""
+    clip_grad uses torch.nn.utils.clip_grad_norm_ and skip_grad costs one host sync.
+    standardize_depth / loss_on_unmasked: the driver's switches of the same names (pretrain_mmae.py:87-89 with :452-458, and
+    :110-111 with :482-486).  The first standardises 'dem' once at the top of each step (standardize_depth()), the standardised
+    tile being both the encoder input and the dem target -- inside the graph too: replay() copies the RAW batch in; the second
+    takes every task loss over all patches (step_losses(loss_on_unmasked=True))."""
 
     def __init__(self, model, optimizer, num_encoded_tokens: int, in_domains=None, alphas: float = 1.0,
                  sample_tasks_uniformly: bool = False, autocast: bool = True, patch_size: int = 16,
                  grad_reducer=None, side_stream_wgrad: bool = False, clip_grad: Optional[float] = None,
                  skip_grad: Optional[float] = None, contra: str = 'dino', contra_weight: Optional[float] = None,
-                 loss_balancer=None, check_finite: bool = True, balancer_lr_scale: float = 1.0):
+                 loss_balancer=None, check_finite: bool = True, balancer_lr_scale: float = 1.0,
+                 standardize_depth: bool = False, loss_on_unmasked: bool = False):
         self.model, self.opt = model, optimizer
         self.in_domains = tuple(in_domains) if in_domains is not None else tuple(model.domains)
         self.N, self.alphas, self.uniform = num_encoded_tokens, alphas, sample_tasks_uniformly
@@ -205,6 +222,7 @@ class PretrainStep:
         self.clip_grad, self.skip_grad, self.check_finite = clip_grad, skip_grad, check_finite
         self.contra, self.contra_weight, self.balancer = contra, contra_weight, loss_balancer
         self.contra_loss = HardNegtive_loss() if contra == 'hardneg' else None
+        self.standardize_depth, self.loss_on_unmasked = standardize_depth, loss_on_unmasked
         # The reference optimises the loss balancer's parameters (UncertaintyWeightingStrategy.log_vars) as the second group of
         # its AdamW (utils/optim_factory.py:136-150, lr x balancer lr_scale).  The flat engine holds the MODEL's parameters
         # only, so a trainable balancer next to a FlatAdamW gets a small companion torch AdamW here -- stepped, zeroed,
@@ -378,12 +396,15 @@ class PretrainStep:
         if getattr(self, "_graph", None) is not None:
             raise RuntimeError("this step has been captured into a hipGraph: use replay() (an eager step would reuse the static mask "
                                "shares and put the optimizer's device-side replay count out of step with the host's)")
+        if self.standardize_depth:
+            tasks_dict = standardize_depth(tasks_dict)    # a new tensor: the raw (captured) input is never overwritten
         x = {t: v for t, v in tasks_dict.items() if t in self.in_domains}
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.autocast):
             out = self.model(x, task_masks=task_masks, num_encoded_tokens=self.N, alphas=self.alphas,
                              sample_tasks_uniformly=self.uniform)
             task_losses, loss_contra, loss = step_losses(out, tasks_dict, out[1], self.patch, self.loss_fns,
-                                                         self.contra_weight, self.contra, self.balancer, self.contra_loss)
+                                                         self.contra_weight, self.contra, self.balancer, self.contra_loss,
+                                                         self.loss_on_unmasked)
         self.opt.zero_grad(set_to_none=True)               # (FlatAdamW: also clears the flat gradient buffer)
         if self.balancer_opt is not None:
             self.balancer_opt.zero_grad(set_to_none=True)
