@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: pretrain samples/s of the native fusion-token path, ViT-B / 3 modalities / 256x256 tiles.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N`: RANK / WORLD_SIZE / MASTER_* in the environment), or -- when WORLD_SIZE is absent -- this process starts
@@ -12,11 +12,14 @@ A step = Dirichlet mask draw + patch embedding of the kept patches + 12 x (Block
 norm + pooling + 3 decoders + masked MSE/L1 + 3 DINO-style contrastive terms + backward + gradient all-reduce (N > 1) +
 AdamW, on synthetic tiles already resident in HBM (BASELINE.md / SURVEY.md 8d).  Prints ONE JSON line on rank 0.
 
-`value` is the resident-input rate of the headline configuration (batch-shared Dirichlet masks, C4 of SURVEY 8d).  At
-N = 1 the same invocation also times two secondary legs on the same model and reports them beside it (never as
-`value`): `pcie_inclusive` -- every step takes a fresh RAW host batch through staging.TileStager (SURVEY 8d's step
-includes the H2D leg) -- and `c3_per_sample_dropout` -- per-sample packed masks with random modality dropout
-(`sample_tasks_uniformly`), the variable-token-count configuration north_star describes.
+`value` is the resident-input rate of the headline configuration (batch-shared Dirichlet masks, C4 of SURVEY 8d).  A plain
+run does only what that figure needs: set-up, warm-up, the timed steps, the dump, the line (its roofline fields come from
+HIP-event brackets inside the timed steps).  `--full` adds, at N = 1, everything that takes runs of its own (see extras()):
+live rocprofv3 counter passes before the timed region, the CPU baseline, and secondary legs timed on the same model after
+it and reported beside `value` (never as `value`): `pcie_inclusive` -- every step takes a fresh RAW host batch through
+staging.TileStager (SURVEY 8d's step includes the H2D leg) --, `c3_per_sample_dropout` -- per-sample packed masks with
+random modality dropout (`sample_tasks_uniformly`), the variable-token-count configuration north_star describes -- and
+`graph_replay`, the step captured into one hipGraph.
 """
 import argparse
 import json
@@ -530,7 +533,24 @@ def dump_outputs(out_dir, model, losses):
             "params_dumped": int(arrays["params"].size)}
 
 
-def main():
+def extras(args):
+    """What the run measures beyond its headline figure -> (secondary legs timed after the main region, live counter passes
+    before it, CPU baseline).  A plain run does none of it.  With --full, `--legs auto` means the pcie, c3 and graph legs at
+    N = 1 with default main settings and the counter passes in the headline configuration only, and the CPU baseline runs at
+    N = 1 unless --no-cpu-baseline.  An explicit --legs list runs as given, with or without --full."""
+    default_main = args.domains == "s1,s2,dem" and args.fusion_blocks and args.contra == "dino" and \
+        not (args.staging or args.per_sample or args.dropout or args.fp32)
+    single = args.gpus == 1
+    if args.legs == "auto":
+        legs = ["pcie", "c3", "graph"] if (args.full and single and default_main) else []
+        counters = bool(args.full and single and default_main and args.model == "base" and args.batch == 256)
+    else:
+        legs = [l for l in args.legs.split(",") if l and l != "none"]
+        counters = single and "mfma" in legs
+    return legs, counters, bool(args.full and single and not args.no_cpu_baseline)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=12)
@@ -549,7 +569,9 @@ def main():
     ap.add_argument("--input-size", dest="input_size", type=int, default=256)
     ap.add_argument("--num-encoded-tokens", dest="num_encoded_tokens", type=int, default=384)
     ap.add_argument("--fp32", action="store_true", help="fp32 compute instead of bf16 autocast")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need (see extras()): at "
+                    "N = 1 the secondary legs, the live counter passes and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-batch", dest="cpu_batch", type=int, default=8)
     ap.add_argument("--cpu-steps", dest="cpu_steps", type=int, default=5)
     ap.add_argument("--bucket-mb", type=int, default=128)
@@ -566,8 +588,8 @@ def main():
     ap.add_argument("--dropout", action="store_true", help="main region: random modality dropout (sample_tasks_uniformly: a "
                     "uniformly drawn non-empty modality subset per mask row, the others get no tokens)")
     ap.add_argument("--legs", default="auto", help="secondary legs timed after the main region: comma list of pcie,c3,graph (+ mfma: the live "
-                    "rocprofv3 MFMA-busy pass in a child process BEFORE the timed region); 'auto' = all at N = 1 with default main settings, none "
-                    "otherwise; 'none'")
+                    "rocprofv3 MFMA-busy pass in a child process BEFORE the timed region); 'auto' = with --full all at N = 1 with default main "
+                    "settings, none otherwise; 'none'")
     ap.add_argument("--clip-grad", dest="clip_grad", type=float, default=0.0, help="> 0: device-side global-norm clipping")
     ap.add_argument("--block-timer", dest="block_timer", type=int, default=1, help="1: HIP-event brackets around encoder layer 6 "
                     "(four events per step) for roofline_block")
@@ -578,7 +600,7 @@ def main():
     ap.add_argument("--dump-outputs", dest="dump_outputs", default="", metavar="DIR", help="after the timed steps, write what the "
                     "last timed step returned (its losses) and the trainable parameters it left (a fixed seeded sample) to DIR/<name>.npy, "
                     "float32, %d MB at most (see dump_outputs)" % (DUMP_MAX_BYTES >> 20))
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.config5:
@@ -586,7 +608,11 @@ def main():
         args.per_sample, args.dropout, args.batch, args.clip_grad = True, True, 64, 1.0
     if not args.fusion_blocks:
         args.contra = "none"                                  # the reference's quadruplet driver trains on the task losses only
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))           # nothing here has touched the GPU yet
     if args.dry_run:
@@ -595,12 +621,10 @@ def main():
     import torch.distributed as dist
     from incomplete_multimodal_fusion_amd import dp, ops
     from incomplete_multimodal_fusion_amd.pretrain import PretrainStep
-    # the live MFMA-busy pass: only for the default invocation at N = 1 (`--legs auto`), and before anything here touches the GPU
-    headline_cfg = args.domains == "s1,s2,dem" and args.fusion_blocks and args.contra == "dino" and args.model == "base" and \
-        not (args.staging or args.per_sample or args.dropout or args.fp32) and args.batch == 256
+    legs, counters, cpu_leg = extras(args)
+    # the live MFMA-busy pass runs before anything here touches the GPU
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)   # (never nest profilers)
-    live_busy = mfma_busy_live(args) if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not profiled and
-                                         (args.legs == "auto" and headline_cfg or "mfma" in args.legs.split(","))) else None
+    live_busy = mfma_busy_live(args) if (counters and "WORLD_SIZE" not in os.environ and not profiled) else None
     if args.tuning_env:
         from tools import tuning_env
         tuning_env.apply()
@@ -688,11 +712,7 @@ def main():
 
     # ---- secondary legs (same model / optimizer state, continuing the run; never `value`) -----------------------------
     default_doms = args.domains == "s1,s2,dem" and args.fusion_blocks and args.contra == "dino"
-    default_main = not (args.staging or args.per_sample or args.dropout or args.fp32) and default_doms
     dpdiag = dp_diagnostics(reducer, world, args.steps, ranks_dt, device, distributed)
-    legs = ("pcie,c3,graph" if (world == 1 and default_main) else "") if args.legs == "auto" else \
-        ("" if args.legs == "none" else args.legs)
-    legs = [l for l in legs.split(",") if l]
     leg_out = {}
     if "pcie" in legs and not args.staging:
         st = make_staged_step()
@@ -871,7 +891,7 @@ def main():
         out.update(leg_out)
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if world == 1 and not args.no_cpu_baseline:
+        if cpu_leg:
             out["cpu_baseline"] = cpu_baseline(args) if default_doms else None      # the CPU leg is the headline configuration's
         print(json.dumps(out), flush=True)
     if distributed:

@@ -71,3 +71,17 @@ def test_bench_gpus8_dry_run_line_carries_the_dp_diagnostics():
     assert d["allreduce_bytes_per_step"] == 2 * nparams and d["buckets_per_step"] >= 2
     assert d["comm_exposed_ms_last_step_max_over_ranks"] >= 0.0
     assert 0.0 < d["rank_ms_per_step_min"] <= d["rank_ms_per_step_max"]
+
+
+def test_plain_run_measures_only_the_headline_and_full_adds_the_rest():
+    """`bench.py --gpus 1 --steps N --warmup W` times its steps and nothing else; --full adds the secondary legs, the live counter
+    passes (headline configuration only) and the CPU baseline at N = 1; an explicit --legs list runs as given."""
+    import bench
+    plain = ["--gpus", "1", "--steps", "3", "--warmup", "1"]
+    assert bench.extras(bench.parse_args(plain)) == ([], False, False)
+    assert bench.extras(bench.parse_args(plain + ["--full"])) == (["pcie", "c3", "graph"], True, True)
+    assert bench.extras(bench.parse_args(plain + ["--full", "--batch", "64"])) == (["pcie", "c3", "graph"], False, True)
+    assert bench.extras(bench.parse_args(plain + ["--full", "--per-sample-masks"])) == ([], False, True)
+    assert bench.extras(bench.parse_args(plain + ["--full", "--no-cpu-baseline", "--legs", "none"])) == ([], False, False)
+    assert bench.extras(bench.parse_args(plain + ["--legs", "graph,mfma"])) == (["graph", "mfma"], True, False)
+    assert bench.extras(bench.parse_args(["--gpus", "2", "--full"])) == ([], False, False)

@@ -14,7 +14,7 @@ for s in $steps; do
   case $s in
     tests) timeout -k 10 1000 python -m pytest tests -m gpu -q -x --timeout 600 > $OUT/tests.log 2>&1; guard $? tests; tail -5 $OUT/tests.log ;;
     testsall) timeout -k 10 1000 python -m pytest tests -m gpu -q --timeout 600 > $OUT/tests.log 2>&1; guard $? tests; tail -15 $OUT/tests.log ;;
-    bench) timeout -k 10 400 python bench.py --steps 12 --warmup 4 > $OUT/bench.json 2> $OUT/bench.err; guard $? bench; cat $OUT/bench.json ;;
+    bench) timeout -k 10 400 python bench.py --steps 12 --warmup 4 --full > $OUT/bench.json 2> $OUT/bench.err; guard $? bench; cat $OUT/bench.json ;;
     stats) rm -rf $OUT/stats; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $BENCH_PROF > $OUT/stats.log 2>&1; guard $? stats ;;
     sq) rm -rf $OUT/sq; timeout -k 10 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY GRBM_GUI_ACTIVE --output-format csv -d $OUT/sq -- python3 $BENCH_PROF > $OUT/sq.log 2>&1; guard $? sq ;;
     hbm) rm -rf $OUT/fetch $OUT/write
