@@ -112,3 +112,74 @@ def test_binding_raises_and_refuses_host_tensors():
         _lib.ptr(torch.zeros(4))
     with pytest.raises(_lib.MmaeLibraryError, match="unsupported dtype"):
         _lib.dt(torch.float16)
+
+
+def test_image_and_loss_argument_checks():
+    l = _lib.lib()
+    buf = (ctypes.c_char * 4096)()
+    a16 = (ctypes.addressof(buf) + 15) // 16 * 16
+    P = ctypes.c_void_p
+    nan = float("nan")
+
+    # every call below breaks exactly one rule; all other arguments are valid (a call with none broken would launch)
+    def patchify(dtype=1, nmod=3, chans=(1, 3, 1), cols=(0, 256, 1024), onehot=1280, Kcat=1288, H=64, W=64, patch=16,
+                 tok_mod=a16, tok_patch=a16):
+        n = max(nmod, 1)
+        imgs = (ctypes.c_void_p * n)(*([a16] * n))
+        ch = (ctypes.c_int * n)(*(list(chans) + [1] * n)[:n])
+        co = (ctypes.c_int * n)(*(list(cols) + [0] * n)[:n])
+        return l.mmae_patchify_gather(dtype, nmod, P(ctypes.addressof(imgs)), P(ctypes.addressof(ch)), P(ctypes.addressof(co)),
+                                      onehot, Kcat, 2, H, W, patch, P(tok_mod), P(tok_patch), 24, P(a16), None)
+    assert patchify(nmod=0) == -1 and patchify(nmod=9, chans=(1,) * 9, cols=tuple(16 * i for i in range(9))) == -1
+    assert patchify(dtype=2) == -1                                          # fp32 / bf16 output only
+    assert patchify(patch=6, H=60, W=60) == -1                              # patch a multiple of 4
+    assert patchify(H=72) == -1 and patchify(W=40) == -1                    # H, W multiples of patch
+    assert patchify(cols=(0, 258, 1024)) == -1                              # column offsets multiples of 4
+    assert patchify(cols=(0, 256, 1036)) == -1                              # slot [1036, 1292) past Kcat 1288
+    assert patchify(onehot=1286) == -1                                      # one-hot offset a multiple of 4
+    assert patchify(onehot=1288) == -1                                      # one-hot block [1288, 1291) past Kcat 1288
+    assert patchify(Kcat=1290) == -1                                        # Kcat % 4
+    assert patchify(tok_mod=0) == -1 and patchify(tok_patch=0) == -1        # both descriptor tables or neither
+    assert patchify(chans=(1, 0, 1)) == -1
+
+    def unpatchify(dtype=1, C=3, H=64, W=64, patch=16):
+        return l.mmae_unpatchify(dtype, 2, C, H, W, patch, P(a16), P(a16), None)
+    assert unpatchify(patch=6, H=60, W=60) == -1 and unpatchify(H=72) == -1 and unpatchify(W=40) == -1
+    assert unpatchify(dtype=2) == -1 and unpatchify(C=0) == -1
+
+    def loss(which, dtype=1, tokens=1, kind=0, B=2, C=3, H=64, W=48, patch=16):
+        if which == "fwd":
+            return l.mmae_masked_loss_fwd(dtype, tokens, kind, B, C, H, W, patch, P(a16), P(a16), None, P(a16), P(a16), P(a16),
+                                          None)
+        return l.mmae_masked_loss_bwd(dtype, tokens, kind, B, C, H, W, patch, P(a16), P(a16), None, P(a16), P(a16), P(a16),
+                                      P(a16), None)
+
+    def ce(which, dtype=1, tokens=1, smooth=0.1, B=2, C=9, H=64, W=48, patch=16):
+        if which == "fwd":
+            return l.mmae_masked_ce_loss_fwd(dtype, tokens, B, C, H, W, patch, P(a16), P(a16), None, smooth, P(a16), P(a16),
+                                             P(a16), None)
+        return l.mmae_masked_ce_loss_bwd(dtype, tokens, B, C, H, W, patch, P(a16), P(a16), None, smooth, P(a16), P(a16), P(a16),
+                                         P(a16), None)
+    for w in ("fwd", "bwd"):
+        for f in (lambda **k: loss(w, **k), lambda **k: ce(w, **k)):
+            assert f(patch=6, H=48, W=48) == -1 and f(patch=0) == -1        # patch a positive multiple of 4
+            assert f(H=72) == -1 and f(W=40) == -1                          # H, W multiples of patch
+            assert f(tokens=0) == -1                                        # the image form is fp32 only (bf16 pred)
+            assert f(dtype=2) == -1 and f(B=0) == -1 and f(C=0) == -1
+        assert loss(w, kind=2) == -1 and loss(w, kind=-1) == -1             # 0 MSE, 1 L1
+        assert ce(w, smooth=-0.01) == -1 and ce(w, smooth=1.01) == -1 and ce(w, smooth=nan) == -1
+
+    def dino(which, B=4, D=256):
+        if which == "fwd":
+            return l.mmae_dino_loss_fwd(B, D, P(a16), P(a16), 0.1, 0.04, P(a16), P(a16), None)
+        return l.mmae_dino_loss_bwd(B, D, P(a16), P(a16), 0.1, 0.04, P(a16), P(a16), None)
+
+    def hardneg(which, B=4, D=64):
+        if which == "fwd":
+            return l.mmae_hardneg_loss_fwd(B, D, P(a16), P(a16), 0.1, 1.0, 0.5, P(a16), P(a16), None)
+        return l.mmae_hardneg_loss_bwd(B, D, P(a16), P(a16), 0.1, 1.0, 0.5, P(a16), P(a16), P(a16), P(a16), None)
+    for w in ("fwd", "bwd"):
+        assert dino(w, D=258) == -1 and dino(w, D=1028) == -1               # D % 4 == 0, D <= 1024 (4 chunks of 64 x 4)
+        assert dino(w, B=0) == -1 and dino(w, D=0) == -1
+        assert hardneg(w, B=1) == -1 and hardneg(w, B=0) == -1              # at least one negative pair: B >= 2
+        assert hardneg(w, D=0) == -1
