@@ -27,7 +27,8 @@ extern "C" {
                                 mmae_mha_bwd_ws_floats, mmae_gemm_nt, mmae_gemm_geglu, mmae_gemm_tn, mmae_splitk_sum_multi.  5: the optimizer control block grew
                                 from 4 to 8 floats (mmae_adamw_control / _step_ctl read [4], [5]); + mmae_adamw_tick, mmae_mha_fwd_route.  6: + mmae_pad_copy_bf16_batched
                                 (additive: no existing signature changed).  7: + mmae_mha_bwd_fused, mmae_mha_bwd_fused_supported, mmae_mha_bwd_fused_ws_floats
-                                (additive); later additive entry points keep 7: mmae_trunc_standardize */
+                                (additive); later additive entry points keep 7: mmae_trunc_standardize, mmae_bilstm_cell1_fwd / _bwd,
+                                mmae_bilstm_cell2_pool_fwd / _bwd */
 int mmae_abi_version(void);
 /* hipError_t of this thread's most recent launch that returned MMAE_ERR_LAUNCH (0: none); reading resets it. */
 int mmae_last_hip_error(void);
@@ -268,6 +269,32 @@ int mmae_stage_tiles(int kind, int in_dtype, int B, int C, int H, int W, int fac
  * mean / stdv: (B) fp32 outputs of mean and sqrt(var + eps), or NULL.  n < 2^31; k_lo >= 0, k_hi <= n, k_hi - k_lo >= 2. */
 int mmae_trunc_standardize(int B, long n, long k_lo, long k_hi, float eps, const float* x, float* y, float* mean, float* stdv,
                            void* stream);
+
+/* ---- two-step BiLSTM fusion + attention pooling (MM/multimae_lstm_s2dsm.py:428-434 with DSI-MM/zorro_utils.py:261-299) ----------
+ * Every row j < R is the length-2 sequence (x0_j, x1_j) through nn.LSTM(D, D, bidirectional), h0 = c0 = 0, gates i, f, g, o;
+ * y_t = h_t^fwd + h_t^rev, s_t = w . tanh(y_t) + b, alpha = softmax(s_0, s_1), r = alpha_0 y_0 + alpha_1 y_1.  The GEMMs are the
+ * caller's: G (2R, 8D) = [x0; x1] . [W_ih_fwd; W_ih_rev]^T (row j: fwd@t0 | rev@t0, row R + j: fwd@t1 | rev@t1, gate blocks of D
+ * columns each), Hf / Hr (R, 4D) = h_fwd@t0 . W_hh_fwd^T / h_rev@t1 . W_hh_rev^T.  bsum (8D) fp32 = [b_ih + b_hh fwd | rev].
+ * G, Hf, Hr, hf, hr, dhf, dhr, dG, dHf, dHr in `dtype`; everything else fp32; cell math fp32.  c1 / h1 / dc1 / dh1: (2, R, D), plane 0
+ * the fwd@t0 cell, plane 1 the rev@t1 cell.  32 <= D <= 1024, D % 32 == 0; R > 0; every pointer 16-byte aligned (b, db: any).
+ * step 1 (nn.LSTM's first time step of each direction): hf / hr (R, D) = h of fwd@t0 / rev@t1 in `dtype` (the recurrent GEMMs'
+ * operands), c1 and h1 in fp32. */
+int mmae_bilstm_cell1_fwd(int dtype, int R, int D, const void* G, const float* bsum, void* hf, void* hr, float* c1, float* h1,
+                          void* stream);
+/* its backward (autograd of the same lines): dh = dhf / dhr + dh1, dc1 from the step-2 cells; writes the step-1 gate gradients
+ * (fwd@t0 and rev@t1 column blocks) of dG (2R, 8D) -- the forget gate's as exact zeros -- and nothing else of dG. */
+int mmae_bilstm_cell1_bwd(int dtype, int R, int D, const void* G, const float* bsum, const void* dhf, const void* dhr,
+                          const float* dc1, const float* dh1, void* dG, void* stream);
+/* step 2 of both directions (fwd@t1, rev@t0) fused with Attention_LSTM and the alpha-weighted sum: r (R, D) fp32, alpha (R, 2). */
+int mmae_bilstm_cell2_pool_fwd(int dtype, int R, int D, const void* G, const void* Hf, const void* Hr, const float* bsum,
+                               const float* c1, const float* h1, const float* w, const float* b, float* r, float* alpha,
+                               void* stream);
+/* its backward: from dr (R, D) fp32 the step-2 gate gradients (fwd@t1 and rev@t0 blocks of dG, and the same values as dHf / dHr),
+ * dc1 / dh1 for step 1, dw (D) and db (1) of the pooling.  ws: 1024 * (D + 1) floats; dw / db are fixed-order sums of per-wave
+ * partials (no atomics: bitwise reproducible). */
+int mmae_bilstm_cell2_pool_bwd(int dtype, int R, int D, const void* G, const void* Hf, const void* Hr, const float* bsum,
+                               const float* c1, const float* h1, const float* w, const float* alpha, const float* dr, void* dG,
+                               void* dHf, void* dHr, float* dc1, float* dh1, float* ws, float* dw, float* db, void* stream);
 
 /* ---- mask bookkeeping (MM/multimae_crossattn.py:233-272 with injected draws; :402-447, :454-462, :489-493) ---------- */
 int mmae_masks_from_draws(int R, int M, int P, int N, const float* dirichlet, const float* noise,

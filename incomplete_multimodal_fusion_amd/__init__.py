@@ -13,13 +13,14 @@ __version__ = "0.1.0"
 def install_as_multimae():
     """Register this package's `multimae` sub-package under the top-level name `multimae`, so that the reference driver's
     own import lines (pretraining/pretrain_mmae.py:35-39: `from multimae.multimae_crossattn import ...`; the 4-modality
-    driver's pretrain_mmae_my.py:35-40: `from multimae.multimae_quadruplet import ...`) resolve to the
+    driver's pretrain_mmae_my.py:35-40: `from multimae.multimae_quadruplet import ...`; the S2+DSM driver's
+    pretrain_mmae_s2dsm.py: `from multimae.multimae_lstm_s2dsm import ...`) resolve to the
     native modules without editing the driver.  Call before the driver is imported."""
     import importlib
     import sys
     native = importlib.import_module(__name__ + ".multimae")
     sys.modules["multimae"] = native
     for sub in ("multimae_crossattn", "zorro_utils", "criterion", "input_adapters", "output_adapters_simple",
-                "multimae_utils", "multimae_quadruplet", "zorro_utils_quadruplet"):
+                "multimae_utils", "multimae_quadruplet", "zorro_utils_quadruplet", "multimae_lstm_s2dsm"):
         sys.modules["multimae." + sub] = importlib.import_module(__name__ + ".multimae." + sub)
     return native

@@ -312,3 +312,71 @@ class Block_Fusion(nn.Module):   # DSI-MM zorro_utils.py:243-258 (canonical)
         xf = x[:, :, -1, :].reshape(B * n, D).float() + o.float()
         xf = xf + self.mlp(xf, pre_gamma=self.norm2.gamma).float()
         return xf.reshape(B, n, D)
+
+
+class _BiLSTMParams(nn.Module):
+    """The parameters of nn.LSTM(D, D, num_layers=1, bidirectional=True) under nn.LSTM's names, in its registration order and with its
+    default initialisation (uniform(-1/sqrt(D), 1/sqrt(D)) over every parameter in that order).  Not an nn.LSTM: nothing of torch's
+    RNN stack (flattened-weight buffers, MIOpen RNN) is built or called; AttentionBiLSTM runs the native kernels on these tensors."""
+    NAMES = ('weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0',
+             'weight_ih_l0_reverse', 'weight_hh_l0_reverse', 'bias_ih_l0_reverse', 'bias_hh_l0_reverse')
+
+    def __init__(self, input_size: int, hidden_size: int):
+        super().__init__()
+        self.input_size, self.hidden_size = input_size, hidden_size
+        shapes = [(4 * hidden_size, input_size), (4 * hidden_size, hidden_size), (4 * hidden_size,), (4 * hidden_size,)] * 2
+        for name, shape in zip(self.NAMES, shapes):
+            setattr(self, name, nn.Parameter(torch.empty(*shape)))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / (self.hidden_size ** 0.5)
+        for w in self.parameters():
+            nn.init.uniform_(w, -stdv, stdv)
+
+    def flat(self):
+        return [getattr(self, n) for n in self.NAMES]
+
+
+class Attention_LSTM(nn.Module):    # DSI-MM zorro_utils.py:261-273
+    """Scores s_t = attention(tanh(H_t)) and their softmax over t.  Its arithmetic runs inside AttentionBiLSTM's pooling kernel
+    (csrc/bilstm.hip); this module holds the reference's `attention` Linear (state-dict key attention.attention.{weight,bias})."""
+
+    def __init__(self, hidden_size):
+        super().__init__()
+        self.attention = nn.Linear(hidden_size, 1)
+
+    def forward(self, H, mask=None):
+        raise NotImplementedError("Attention_LSTM is computed inside AttentionBiLSTM's fused kernel (ops.bilstm2_attn_pool); "
+                                  "there is no standalone path")
+
+
+class AttentionBiLSTM(nn.Module):   # DSI-MM zorro_utils.py:276-299
+    """y = BiLSTM(embedded) with the two directions summed, alpha = Attention_LSTM(y), r = alpha . y -- on native kernels
+    (ops.bilstm2_attn_pool).  Documented limit: sequences of length 2 only (the one length the reference model uses,
+    multimae_lstm_s2dsm.py:428-434), one layer; `mask` is not supported (the model passes None)."""
+
+    def __init__(self, embedding_dim, num_layers=1, dropout=0.0, emb_layer_dropout=0.0):
+        super().__init__()
+        if num_layers != 1:
+            raise ValueError("AttentionBiLSTM: one layer only (the reference model's configuration)")
+        self.embedding_dim = embedding_dim
+        self.lstm = _BiLSTMParams(embedding_dim, embedding_dim)
+        self.attention = Attention_LSTM(embedding_dim)
+
+    def pool_pairs(self, x0, x1):
+        """x0, x1 (R, D): the two time steps of each sequence -> r (R, D) fp32."""
+        a = self.attention.attention
+        return ops.bilstm2_attn_pool(x0, x1, self.lstm.flat(), a.weight, a.bias)
+
+    def forward(self, embedded, mask=None):
+        if mask is not None:
+            raise ValueError("AttentionBiLSTM: mask is not supported")
+        if embedded.dim() != 3 or embedded.shape[1] != 2 or embedded.shape[2] != self.embedding_dim:
+            raise ValueError("AttentionBiLSTM: (R, 2, %d) input expected, got %s (sequence length 2 only)"
+                             % (self.embedding_dim, tuple(embedded.shape)))
+        return self.pool_pairs(_c2(embedded[:, 0]), _c2(embedded[:, 1]))
+
+
+def _c2(t):
+    return t if t.is_contiguous() else t.contiguous()

@@ -1602,3 +1602,108 @@ class Descriptors:
         bad = int(self.status[0].item())
         if bad:
             raise AssertionError("%d sample(s): number of kept tokens != num_encoded_tokens" % bad)
+
+
+# ------------------------------------------------------------------------------------------------ two-step BiLSTM fusion
+class _BiLSTMGrad:
+    """The (2R, 8D) gate-gradient buffer shared by the two cell nodes of one bilstm2_attn_pool call: the step-2 node's backward
+    (which runs first) writes its column blocks, the step-1 node's backward the others and hands the whole buffer to the input
+    projection -- one buffer, no full-size sum of two half-empty gradients."""
+    __slots__ = ("dG",)
+
+    def __init__(self):
+        self.dG = None
+
+
+class _BiLSTMCell1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, G, bsum, state):
+        R, D = G.shape[0] // 2, G.shape[1] // 8
+        hf = torch.empty(R, D, dtype=G.dtype, device=G.device)
+        hr = torch.empty_like(hf)
+        c1 = torch.empty(2, R, D, dtype=torch.float32, device=G.device)
+        h1 = torch.empty_like(c1)
+        call("mmae_bilstm_cell1_fwd", dt(G), R, D, ptr(G), ptr(bsum), ptr(hf), ptr(hr), ptr(c1), ptr(h1), stream())
+        ctx.save_for_backward(G, bsum)
+        ctx.state = state
+        return hf, hr, c1, h1
+
+    @staticmethod
+    def backward(ctx, dhf, dhr, dc1, dh1):
+        G, bsum = ctx.saved_tensors
+        R, D = G.shape[0] // 2, G.shape[1] // 8
+        st = ctx.state
+        dG = st.dG if st.dG is not None else torch.zeros_like(G)
+        st.dG = None
+        dhf, dhr = _c(dhf.to(G.dtype)), _c(dhr.to(G.dtype))
+        call("mmae_bilstm_cell1_bwd", dt(G), R, D, ptr(G), ptr(bsum), ptr(dhf), ptr(dhr), ptr(_c(dc1)), ptr(_c(dh1)), ptr(dG),
+             stream())
+        return dG, (colsum(dG) if ctx.needs_input_grad[1] else None), None
+
+
+class _BiLSTMCell2Pool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, G, Hf, Hr, bsum, c1, h1, w, b, state):
+        R, D = G.shape[0] // 2, G.shape[1] // 8
+        r = torch.empty(R, D, dtype=torch.float32, device=G.device)
+        alpha = torch.empty(R, 2, dtype=torch.float32, device=G.device)
+        call("mmae_bilstm_cell2_pool_fwd", dt(G), R, D, ptr(G), ptr(Hf), ptr(Hr), ptr(bsum), ptr(c1), ptr(h1), ptr(w), ptr(b),
+             ptr(r), ptr(alpha), stream())
+        ctx.save_for_backward(G, Hf, Hr, bsum, c1, h1, w, alpha)
+        ctx.state = state
+        return r
+
+    @staticmethod
+    def backward(ctx, dr):
+        G, Hf, Hr, bsum, c1, h1, w, alpha = ctx.saved_tensors
+        R, D = G.shape[0] // 2, G.shape[1] // 8
+        dG = torch.empty_like(G)
+        dHf, dHr = torch.empty_like(Hf), torch.empty_like(Hr)
+        dc1, dh1 = torch.empty_like(c1), torch.empty_like(h1)
+        ws = torch.empty(1024 * (D + 1), dtype=torch.float32, device=G.device)
+        dw = torch.empty(D, dtype=torch.float32, device=G.device)
+        db = torch.empty(1, dtype=torch.float32, device=G.device)
+        call("mmae_bilstm_cell2_pool_bwd", dt(G), R, D, ptr(G), ptr(Hf), ptr(Hr), ptr(bsum), ptr(c1), ptr(h1), ptr(w), ptr(alpha),
+             ptr(_c(dr.float())), ptr(dG), ptr(dHf), ptr(dHr), ptr(dc1), ptr(dh1), ptr(ws), ptr(dw), ptr(db), stream())
+        ctx.state.dG = dG                 # completed by _BiLSTMCell1.backward, which returns it
+        return None, dHf, dHr, None, dc1, dh1, dw.view(1, D), db, None
+
+
+def bilstm2_attn_pool(x0: torch.Tensor, x1: torch.Tensor, lstm_params: Sequence[torch.Tensor], w: torch.Tensor, b: torch.Tensor,
+                      compute_dtype=None) -> torch.Tensor:
+    """AttentionBiLSTM on R length-2 sequences (DSI-MM/zorro_utils.py:284-299 with nn.LSTM(D, D, bidirectional=True),
+    h0 = c0 = 0): x0, x1 (R, D) are time steps 0 and 1; lstm_params = (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, and the
+    same four _reverse); w (1, D), b (1,) = Attention_LSTM's Linear.  -> r (R, D) fp32 = alpha_0 y_0 + alpha_1 y_1.
+    The input projection of both steps and directions is one GEMM, the recurrent projection one GEMM per direction (ops.linear,
+    each weight once per call); between them the cell kernels of csrc/bilstm.hip, cell math in fp32.  compute_dtype: the GEMM
+    operand dtype (default: bf16 under autocast, else fp32)."""
+    w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r = lstm_params
+    R, D = x0.shape
+    if x1.shape != (R, D) or tuple(w_ih.shape) != (4 * D, D) or tuple(w.shape) != (1, D):
+        raise ValueError("bilstm2_attn_pool: x0 / x1 (R, D), weight_ih (4D, D), attention weight (1, D) expected")
+    if compute_dtype is None:
+        compute_dtype = torch.bfloat16 if torch.is_autocast_enabled("cuda") else torch.float32
+    T = compute_dtype
+    X = torch.cat([x0.to(T), x1.to(T)], dim=0)                                          # (2R, D)
+    G = linear(X, [w_ih, w_ih_r], once=True)                                            # (2R, 8D)
+    bsum = torch.cat([b_ih.float() + b_hh.float(), b_ih_r.float() + b_hh_r.float()])    # (8D) fp32
+    state = _BiLSTMGrad()
+    hf, hr, c1, h1 = _BiLSTMCell1.apply(G, bsum, state)
+    Hf = linear(hf, w_hh, once=True)                                                    # (R, 4D)
+    Hr = linear(hr, w_hh_r, once=True)
+    return _BiLSTMCell2Pool.apply(G, _c(Hf), _c(Hr), bsum, c1, h1, _c(w.float()), _c(b.float()), state)
+
+
+def last_wins_fusion(enc_fus: torch.Tensor, learned: torch.Tensor, slot_row: torch.Tensor, B: int, P: int, M: int, BN: int):
+    """The decoders' (B*P, D) input of the S2+DSM model (MM/multimae_lstm_s2dsm.py:473-476): row b*P + p is the encoder fusion row
+    of the LAST modality (in modality order) that keeps patch p of sample b -- the reference's loop overwrites in that order --
+    or the learned fusion token `learned[p]` (P, D) where no modality keeps it.  enc_fus: (B*N, D) encoder fusion rows, row
+    b*N + i for the i-th kept token of sample b; slot_row: Descriptors.slot_row (token rows are < BN, packed modality-major, so the
+    winner is the largest kept row).  Winner per patch on the device, no host sync; the backward is a row scatter (winners are
+    unique) plus a fixed-order sum over the batch for the learned rows.  Output in enc_fus's dtype."""
+    D = enc_fus.shape[1]
+    s = slot_row[:, :M]
+    win = torch.where(s < BN, s, torch.full_like(s, -1)).amax(dim=1)                   # (B*P,) int32, -1: no modality kept it
+    idx_learned = torch.where(win < 0, torch.arange(B * P, dtype=torch.int32, device=win.device), torch.full_like(win, -1))
+    learned_rows = learned.to(enc_fus.dtype).unsqueeze(0).expand(B, P, D).reshape(B * P, D)
+    return gather_rows(enc_fus, _c(win)) + gather_rows(_c(learned_rows), _c(idx_learned))

@@ -45,14 +45,20 @@ PRESETS = {'tiny': (192, 12, 3), 'small': (384, 12, 8), 'base': (768, 12, 8), 'l
 def get_model(model: str = 'base', in_domains=('s1', 's2', 'dem'), out_domains=None, patch_size: int = 16,
               input_size: int = 256, decoder_dim: int = 256, decoder_depth: int = 2, decoder_num_heads: int = 8,
               dim_head: int = 64, domain_conf: Optional[dict] = None, fusion_blocks: bool = True, drop_path_rate: float = 0.0,
-              decoder_drop_path_rate: float = 0.0):
+              decoder_drop_path_rate: float = 0.0, fusion: str = 'tokens'):
     """Adapters + model as get_model builds them (pretrain_mmae.py:193-246); `model` picks the size preset (the
     reference ignores --model and always builds the tiny factory, :239 -- SURVEY.md 0.5).  `domain_conf` defaults to the
     3-modality table, or to the 4-modality one when 'dnw' is among the domains.
     fusion_blocks=False builds the reference's own 4-modality model (multimae_quadruplet.MultiMAE, what
     pretrain_mmae_my.py:248-255 builds: Zorro-masked blocks only, 5-tuple output; pinned by tests/golden/quad_tiny.npz).
     NOTE: the reference has no M = 4 model WITH fusion blocks; fusion_blocks=True with four domains is this package's
-    extension of the 3-modality algorithm to M modalities and has no reference-generated fixture."""
+    extension of the 3-modality algorithm to M modalities and has no reference-generated fixture.
+    fusion='bilstm' with in_domains=('s2', 'dem') builds the S2+DSM driver's model (pretrain_mmae_s2dsm.py:181-241:
+    multimae_lstm_s2dsm.MultiMAE, return tokens (S2, DEM, FUSION); pinned by tests/golden/s2dsm_tiny.npz)."""
+    if fusion not in ('tokens', 'bilstm'):
+        raise ValueError("fusion must be 'tokens' or 'bilstm'")
+    if fusion == 'bilstm' and tuple(in_domains) != ('s2', 'dem'):
+        raise ValueError("fusion='bilstm' is the S2+DSM model: in_domains=('s2', 'dem')")
     out_domains = tuple(in_domains) if out_domains is None else tuple(out_domains)
     conf = domain_conf or (DOMAIN_CONF_QUAD if 'dnw' in in_domains else DOMAIN_CONF)
 
@@ -76,7 +82,9 @@ def get_model(model: str = 'base', in_domains=('s1', 's2', 'dem'), out_domains=N
     D, depth, heads = PRESETS[model]
     P = (input_size // patch_size) ** 2
     M = len(in_domains)
-    if tuple(in_domains) == ('s1', 's2', 'dem'):
+    if fusion == 'bilstm':
+        rtt = (TokenTypes.S2, TokenTypes.DEM, TokenTypes.FUSION)                   # pretrain_mmae_s2dsm.py:236
+    elif tuple(in_domains) == ('s1', 's2', 'dem'):
         rtt = (TokenTypes.S1, TokenTypes.S2, TokenTypes.DEM, TokenTypes.FUSION)
     elif tuple(in_domains) == ('s1', 's2', 'dem', 'dnw'):
         rtt = tuple(TokenTypesQuad)
@@ -84,7 +92,10 @@ def get_model(model: str = 'base', in_domains=('s1', 's2', 'dem'), out_domains=N
         from enum import Enum
         rtt = tuple(Enum('TokenTypesM', [(d.upper(), i) for i, d in enumerate(in_domains)] + [('FUSION', M)]))
     cls = mc.MultiMAE
-    if not fusion_blocks:
+    if fusion == 'bilstm':
+        from .multimae import multimae_lstm_s2dsm
+        cls = multimae_lstm_s2dsm.MultiMAE
+    elif not fusion_blocks:
         from .multimae import multimae_quadruplet
         cls = multimae_quadruplet.MultiMAE
     return cls(input_adapters=input_adapters, output_adapters=output_adapters, num_global_tokens=1,
