@@ -8,6 +8,9 @@ feature taps after the layers in `flags`.  What differs from pretraining and is 
 absent from the forward gets NO slot in the modality attention (:635-648 builds M'+1 slots), whereas a masked patch of a
 present modality still reads mask_embedding.  The four necks (ConvTranspose2d / GroupNorm / GELU / MaxPool2d) are
 ordinary torch modules -- library ops outside the hot path.
+
+Shared with multimae_crossattn.MultiMAE (defined there once): constructor, geometry, masks -> descriptors, and the whole
+encoder (_encode).  Owned here: the per-forward modality subset and kept-token count, the feature taps and the necks.
 """
 import os
 import random
@@ -60,27 +63,14 @@ class ViTBaseline(MultiMAE):
         one_mod = self.incomplete_domains[0]
         x = {one_mod: x} if isinstance(x, torch.Tensor) else x
         present = [d for d in x if d in self.input_adapters and d in self.incomplete_domains]       # dict order (:560-564)
-        B, _, H, W = x[present[0]].shape
-        device = x[present[0]].device
-        ps = self.input_adapters[present[0]].P_H
-        N_H, N_W = H // ps, W // ps
-        P = N_H * N_W
+        _, _, _, _, N_H, N_W, P, _ = self._geometry(x, present)
         Mp = len(present)
         if mask_inputs:
             N = num_encoded_tokens
         else:
             N = int(Mp * P * 0.9) if self.training else Mp * P                                       # :577-582
-        if task_masks is None:
-            placeholders = {d: torch.empty(B, P, 0, device=device) for d in present}
-            task_masks, _, _ = self.generate_random_masks(placeholders, N, alphas=alphas,
-                                                          sample_tasks_uniformly=sample_tasks_uniformly)
-            mask_all = torch.cat([task_masks[d][:(B if self.per_sample_masks else 1)] for d in present], dim=1)
-            explicit = False
-        else:
-            mask_full = torch.cat([task_masks[d] for d in present], dim=1).to(torch.int64)
-            mask_all = mask_full if self.per_sample_masks else mask_full[:1]
-            explicit = True
-        _, _, _, _, outs = self._encode(x, present, mask_all.contiguous(), N, explicit, taps=tuple(self.flags))
+        _, desc = self._descriptors(x, present, N, task_masks, alphas, sample_tasks_uniformly)
+        _, _, _, outs = self._encode(x, present, desc, taps=tuple(self.flags))
         return outs, N_H, N_W
 
     def forward(self, input_dict):

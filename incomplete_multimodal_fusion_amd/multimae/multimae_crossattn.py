@@ -14,7 +14,15 @@ Exact algebraic shortcuts relative to the reference (rows are independent, resul
   * Block_Fusion evaluates the query / output projection of the fusion slot only (reference computes all M+1 slots and
     discards M of them, zorro_utils.py:255-256) and K/V of masked slots once per patch (they come from mask_embedding);
   * the (B,P,M+1,D) `all_tokens` tensor (:454-462) and the (B,h,S,S) score tensor are never materialised.
+
+The class here is also the base of the other models on this pipeline (multimae_quadruplet, multimae_lstm_s2dsm, and the downstream
+multimae_big_imcomplete.ViTBaseline).  Stages with ONE definition here, called by every model: the constructor prologue
+(_init_shared), input validation and geometry (_begin / _geometry), masks -> descriptors (_descriptors), patch embedding of the
+kept patches (_embed_kept), attention pooling (_attn_pool), the decoder loop (_decode), one_delta and the preset _factory.  Owned
+by this file: the Block_Fusion + Block layer loop (_encode), the fused pool-K/V + decoder-context GEMM, the final norm with its
+bf16 copy, and the contrastive return tokens.
 """
+import contextlib
 import itertools
 import math
 from collections import OrderedDict
@@ -37,8 +45,19 @@ __all__ = ['pretrain_multimae_tiny', 'pretrain_multimae_base', 'pretrain_multima
 FUSED_FINAL_CAST = True     # bf16 copy of the final norm's output from the same pass
 FUSED_DECODER_CTX = True    # one GEMM for every decoder's proj_context
 DUAL_LAYERNORM = True       # one pass for the modality rows' two LayerNorm pairs
-DECODER_STREAMS = False     # the per-modality decoders on separate HIP streams (measured: no gain)
 ASYNC_DRAW_COPY = True          # the Dirichlet draw reaches the device through pinned memory, asynchronously (generate_random_masks)
+
+
+def one_delta(a, a_off, b, b_off):
+    """parts_add_ln takes ONE delta tensor; the two pending deltas (modality part / fusion part, each a tensor and its row offset)
+    are either the same tensor or one is None."""
+    if a is None:
+        return b, -1, b_off
+    if b is None:
+        return a, a_off, -1
+    assert a is b
+    return a, a_off, b_off
+
 
 class PredTokens:
     """Decoder output kept token-major, (B*P, C*p*p) in (c ph pw) order, so that the masked loss can be fused with the
@@ -77,35 +96,18 @@ class MultiMAE(nn.Module):
         sibling pretraining/multimae/multimae_quadruplet.py model -- same encoder without the per-layer Block_Fusion, without
         mask_embedding and without the per-modality contrastive return tokens (see multimae_quadruplet.py here)."""
         super().__init__()
-        for adapter in input_adapters.values():
-            adapter.init(dim_tokens=dim_tokens)
-        self.input_adapters = nn.ModuleDict(input_adapters)
-        if output_adapters is not None:
-            for adapter in output_adapters.values():
-                adapter.init(dim_tokens_enc=dim_tokens)
-            self.output_adapters = nn.ModuleDict(output_adapters)
-        else:
-            self.output_adapters = None
-        self.domains = [d for d in input_adapters if d != 'fusion']
+        domains = [d for d in input_adapters if d != 'fusion']
         assert num_fusion_tokens == input_adapters['s1'].num_patches          # reference :87
         # Any number M <= 7 of modalities (the reference hard-codes s1/s2/dem, :402-407; its 4-modality sibling
         # multimae_quadruplet.py adds dnw): one return token per modality in adapter order, then the fusion type last --
         # the pool / Zorro rules are built from that order on the device (csrc/masks.hip).
-        M = len(self.domains)
+        M = len(domains)
         assert 1 <= M <= 7, "1..7 modalities"
         assert len(return_token_types) == M + 1, "one return token per modality plus fusion"
         assert [t.value for t in return_token_types] == list(range(M + 1)), \
             "return_token_types must be (modality 0, ..., modality M-1, FUSION) with values 0..M"
-
-        self.dim_tokens, self.depth, self.heads, self.dim_head = dim_tokens, depth, heads, dim_head
-        self.max_return_tokens = len(return_token_types)
-        self.return_token_types = return_token_types
-        self.register_buffer('return_token_types_tensor',
-                             torch.tensor([t.value for t in return_token_types]), persistent=False)
-
-        self.return_tokens = nn.Parameter(trunc_normal_(torch.zeros(1, self.max_return_tokens, dim_tokens), std=0.02))
-        self.attn_pool = Attention(dim=dim_tokens, dim_head=dim_head, heads=heads)
-        self.fusion_tokens = nn.Parameter(trunc_normal_(torch.zeros(1, num_fusion_tokens, dim_tokens), std=0.02))
+        self._init_shared(input_adapters, output_adapters, domains, dim_tokens, depth, dim_head, heads, num_fusion_tokens,
+                          return_token_types)
         self.has_fusion_blocks, self.has_contrastive_tokens = bool(fusion_blocks), bool(contrastive_tokens)
         self.dual_layernorm = DUAL_LAYERNORM
         if contrastive_tokens:
@@ -123,17 +125,39 @@ class MultiMAE(nn.Module):
             for i in range(depth)])
         self.norm = LayerNorm(dim_tokens)
 
+        self._reset_parameters()
+
+    def _init_shared(self, input_adapters, output_adapters, domains, dim_tokens, depth, dim_head, heads, num_fusion_tokens,
+                     return_token_types):
+        """Constructor prologue of every model on the packed pipeline (after nn.Module.__init__): what they all register first, in
+        the reference's order -- the adapters, then return_tokens, attn_pool, fusion_tokens -- and the switches of the native path.
+        `domains`: the modality order of the packed row space."""
+        for adapter in input_adapters.values():
+            adapter.init(dim_tokens=dim_tokens)
+        self.input_adapters = nn.ModuleDict(input_adapters)
+        if output_adapters is not None:
+            for adapter in output_adapters.values():
+                adapter.init(dim_tokens_enc=dim_tokens)
+            self.output_adapters = nn.ModuleDict(output_adapters)
+        else:
+            self.output_adapters = None
+        self.domains = list(domains)
+        self.dim_tokens, self.depth, self.heads, self.dim_head = dim_tokens, depth, heads, dim_head
+        self.max_return_tokens = len(return_token_types)
+        self.return_token_types = return_token_types
+        self.register_buffer('return_token_types_tensor',
+                             torch.tensor([t.value for t in return_token_types]), persistent=False)
+        self.return_tokens = nn.Parameter(trunc_normal_(torch.zeros(1, self.max_return_tokens, dim_tokens), std=0.02))
+        self.attn_pool = Attention(dim=dim_tokens, dim_head=dim_head, heads=heads)
+        self.fusion_tokens = nn.Parameter(trunc_normal_(torch.zeros(1, num_fusion_tokens, dim_tokens), std=0.02))
+
         # behaviour switches of the native path (not part of the reference API)
         self.per_sample_masks = False      # True: every sample draws / uses its own mask row (packed superset)
         self.fuse_unpatchify_loss = False  # True: preds are PredTokens (fused unpatchify + masked loss)
         self.check_masks = True            # explicit task_masks: verify kept count == num_encoded_tokens (host sync)
-        self.decoder_streams = DECODER_STREAMS
-        self._dec_streams = []
         self.side_stream_wgrad = False     # True: encoder weight-gradient GEMMs overlap the backward chain on a side
                                            # stream; the trainer must ops.join_wgrad_stream() before reading .grad
         self.layer_timer = None            # an ops.LayerTimer: HIP-event brackets around that encoder layer (bench.py roofline_block)
-
-        self._reset_parameters()
 
     # ---- initialisation: same distributions as the reference (:140-165) ------------------------------------------------
     def _reset_parameters(self):
@@ -244,55 +268,93 @@ class MultiMAE(nn.Module):
         info['num_task_tokens'] = i
         return info
 
-    # ---- packed encoder shared by the pretraining forward and the downstream backbone ------------------------------------
-    def _encode(self, x, doms, mask_all, N, explicit, taps=()):
-        """Patch-embed the kept patches of modalities `doms`, then run the depth x (Block_Fusion + Block) stack on the
-        packed row space.  Returns (descriptors, xm, xf, pending residual deltas, tap list): the residual stream is
-        (xm, xf) PLUS the pending deltas, which the caller's next add+LayerNorm pass folds in.  `taps`: layer indices
-        after which the fusion tokens (B, P, D) are materialised (downstream feature taps)."""
-        B, H, W = x[doms[0]].shape[0], x[doms[0]].shape[-2], x[doms[0]].shape[-1]
-        device = x[doms[0]].device
-        M, D, Hh, dh = len(doms), self.dim_tokens, self.heads, self.dim_head
+    # ---- stages shared by every model on the packed pipeline ----------------------------------------------------------------
+    def _geometry(self, x, doms):
+        """(B, H, W, patch size, grid rows, grid columns, P, device) of one forward: batch and image size from the first
+        modality of `doms` (all share one patch grid on this path), the patch size from its adapter."""
+        img = x[doms[0]]
+        B, H, W = img.shape[0], img.shape[-2], img.shape[-1]
         ps = self.input_adapters[doms[0]].P_H
         nh, nw = H // ps, W // ps
-        P = nh * nw
-        T = compute_dtype(self.fusion_tokens)
-        desc = ops.Descriptors(mask_all.contiguous(), B, M, P, N)
+        return B, H, W, ps, nh, nw, nh * nw, img.device
+
+    def _begin(self, x, first, mask_inputs, num_encoded_tokens, return_token_indices):
+        """Input validation of a pretraining forward (reference :360, :402-407, :478-484).  `first`: the modality a bare tensor
+        stands for; its tensor gives the batch and image size.  Returns (x as a dict, B, H, W, P, N kept tokens per sample, compute dtype)."""
+        x = {first: x} if isinstance(x, torch.Tensor) else x
+        B, _, H, W = x[first].shape                     # KeyError without it, as in the reference (:360)
+        for d in self.domains:
+            _ = x[d]                                    # every configured modality must be present (:402-407)
+        if exists(return_token_indices):                # reference :478-484
+            assert len(set(return_token_indices)) == len(return_token_indices), 'all indices must be unique'
+            assert all(i < self.max_return_tokens for i in return_token_indices), \
+                'indices must range from 0 to max_num_return_tokens - 1'
+        ps = self.input_adapters[self.domains[0]].P_H
+        P = (H // ps) * (W // ps)
+        assert P == self.fusion_tokens.shape[1], "fusion tokens are tied to the patch grid (reference :87)"
+        N = num_encoded_tokens if mask_inputs else len(self.domains) * P
+        return x, B, H, W, P, N, compute_dtype(self.fusion_tokens)
+
+    def _descriptors(self, x, doms, N, task_masks, alphas, sample_tasks_uniformly):
+        """Masks + device-side descriptors of the modalities `doms` (no host sync on the random path): task_masks None draws
+        random masks, else the given ones are used (and checked, see check_masks); row 0 drives the batch unless
+        per_sample_masks.  Returns (task_masks, ops.Descriptors)."""
+        B, _, _, _, _, _, P, device = self._geometry(x, doms)
+        explicit = task_masks is not None
+        if explicit:
+            mask_full = torch.cat([task_masks[d] for d in doms], dim=1).to(torch.int64)
+            mask_all = mask_full if self.per_sample_masks else mask_full[:1]      # row 0 drives the batch (:402-406)
+        else:
+            placeholders = {d: torch.empty(B, P, 0, device=device) for d in doms}
+            task_masks, _, _ = self.generate_random_masks(placeholders, N, alphas=alphas,
+                                                          sample_tasks_uniformly=sample_tasks_uniformly)
+            mask_all = torch.cat([task_masks[d][:(B if self.per_sample_masks else 1)] for d in doms], dim=1)
+        desc = ops.Descriptors(mask_all.contiguous(), B, len(doms), P, N)
         if explicit and self.check_masks:
             desc.check()
-        BN, BP = B * N, B * P
+        return task_masks, desc
 
-        # -- patch embedding of the kept patches: one gather kernel + one GEMM for all modalities --------------------------
-        Ks = [self.input_adapters[d].packed_channels * ps * ps for d in doms]
+    def _embed_kept(self, x, doms, desc):
+        """Patch embedding of the kept patches of modalities `doms`: one gather kernel + one GEMM for all modalities (the
+        biases ride along as one-hot columns).  Returns (tok, pe): the projected patches (B*N, D) in the compute dtype, bias
+        included, and their pos-emb rows (B*N, D) in fp32."""
+        _, _, _, ps, nh, nw, _, _ = self._geometry(x, doms)
+        M, D = len(doms), self.dim_tokens
+        ads = [self.input_adapters[d] for d in doms]
+        Ks = [a.packed_channels * ps * ps for a in ads]
         koff = [sum(Ks[:i]) for i in range(M)]
         onehot = sum(Ks)
         Kcat = onehot + ((M + 7) // 8) * 8
-        pcat = ops.patchify_gather([self.input_adapters[d].packed_image(x[d]) for d in doms], koff, onehot, Kcat, ps,
-                                   desc.tok_mod, desc.tok_patch, N, T)
-        wcat = torch.cat([self.input_adapters[d].packed_weight() for d in doms] +
-                         [torch.stack([self.input_adapters[d].packed_bias() for d in doms], dim=1),
+        pcat = ops.patchify_gather([a.packed_image(x[d]) for d, a in zip(doms, ads)], koff, onehot, Kcat, ps,
+                                   desc.tok_mod, desc.tok_patch, desc.N, compute_dtype(self.fusion_tokens))
+        wcat = torch.cat([a.packed_weight() for a in ads] +
+                         [torch.stack([a.packed_bias() for a in ads], dim=1),
                           pcat.new_zeros(D, Kcat - onehot - M, dtype=torch.float32)], dim=1)
         tok = linear(pcat, wcat, once=True)                                                   # (B*N, D), bias included
-        pe_table = torch.cat([interp_posemb(self.input_adapters[d].pos_emb, nh, nw) for d in doms], dim=0)
+        pe_table = torch.cat([interp_posemb(a.pos_emb, nh, nw) for a in ads], dim=0)
         if pe_table.requires_grad:
-            xm = pe_table.index_select(0, desc.tok_pe.long())
+            pe = pe_table.index_select(0, desc.tok_pe.long())
         else:
-            xm = ops.gather_rows(pe_table.detach().contiguous(), desc.tok_pe)      # (B*N, D) fp32
+            pe = ops.gather_rows(pe_table.detach().contiguous(), desc.tok_pe)      # (B*N, D) fp32
+        return tok, pe
+
+    # ---- packed encoder shared by the pretraining forward and the downstream backbone ------------------------------------
+    def _encode(self, x, doms, desc, taps=()):
+        """Patch-embed the kept patches of modalities `doms`, then run the depth x (Block_Fusion + Block) stack on the
+        packed row space.  Returns (xm, xf, pending residual deltas, tap list): the residual stream is
+        (xm, xf) PLUS the pending deltas, which the caller's next add+LayerNorm pass folds in.  `taps`: layer indices
+        after which the fusion tokens (B, P, D) are materialised (downstream feature taps)."""
+        B, P, N = desc.B, desc.P, desc.N
+        M, D, Hh, dh = len(doms), self.dim_tokens, self.heads, self.dim_head
+        T = compute_dtype(self.fusion_tokens)
+        BN, BP = B * N, B * P
+        tok, xm = self._embed_kept(x, doms, desc)
         fus_pe = self.input_adapters['fusion'].posemb_rows()
         xf = (self.fusion_tokens[0] + fus_pe).unsqueeze(0).expand(B, P, D).reshape(BP, D).contiguous()
         me = self.mask_embedding[0].contiguous() if self.has_fusion_blocks else None   # (P, D) shared rows
         # pending residual deltas (compute dtype): modality part / fusion part, as (tensor, row offset)
         dm, dm_off, df, df_off = tok, 0, None, -1
         tap_out = []
-
-        def one_delta(a, a_off, b, b_off):
-            """parts_add_ln takes ONE delta tensor; the two pending deltas are either the same tensor or one is None."""
-            if a is None:
-                return b, -1, b_off
-            if b is None:
-                return a, a_off, -1
-            assert a is b
-            return a, a_off, b_off
 
         sw = self.side_stream_wgrad
         lt = self.layer_timer
@@ -346,7 +408,44 @@ class MultiMAE(nn.Module):
             if l in taps:
                 tap_out.append((xf + f[BN:BN + BP].float()).reshape(B, P, D))
 
-        return desc, xm, xf, (dm, dm_off, df, df_off), tap_out
+        return xm, xf, (dm, dm_off, df, df_off), tap_out
+
+    def _attn_pool(self, queries, kv, q_seg, kv_seg, B, empty_mode, indices=None):
+        """Attention pooling (:475-497, :530-543): the learned `queries` (n, D), the same for every sample, attend the projected
+        K/V rows `kv` under the segment rule (q_seg, kv_seg), then to_out and the residual Mlp under self.norm.  Returns
+        (B, n, D) fp32, or the rows `indices` of it (each query row is independent)."""
+        ap = self.attn_pool
+        T = compute_dtype(self.fusion_tokens)
+        q = linear(ops.layernorm(queries, ap.norm.gamma, out_dtype=T), ap.to_q.weight)      # (n, heads * dim_head)
+        a = ops.mha_cross(q.repeat(B, 1), kv, self.heads, self.dim_head, q_seg, kv_seg, ap.scale, empty_mode=empty_mode)
+        pooled = linear(a, ap.to_out.weight).float()                                        # (B*n, D)
+        pooled = pooled + self.mlp(ops.layernorm(pooled, self.norm.gamma, out_dtype=T)).float()
+        pooled = pooled.reshape(B, queries.shape[0], self.dim_tokens)
+        if exists(indices):
+            pooled = pooled[:, torch.tensor(list(indices), dtype=torch.long, device=pooled.device)]
+        return pooled
+
+    def _decode(self, B, H, W, rows_of, fp32_output_adapters, ctx_rows=None):
+        """The decoder loop (:507-527): every output adapter on the (B*P, D) rows `rows_of(fp32)`, then the unpatchify -- or
+        PredTokens when fuse_unpatchify_loss leaves it to the fused loss.  fp32: the adapter is named in fp32_output_adapters;
+        it gets fp32 rows and runs outside the autocast region, as the reference's do (layer_norm leaves an autocast region
+        in fp32).  `ctx_rows` (task -> rows): the context projections came out of one fused GEMM already, the adapters
+        enter at decode_rows (never with fp32 adapters).  Returns {task: prediction}."""
+        P = self.fusion_tokens.shape[1]
+        dec_seg = ops.Segments.dense(B, P, self.fusion_tokens.device)
+        preds = {}
+        for d, adapter in self.output_adapters.items():
+            if ctx_rows is not None:
+                tk = adapter.decode_rows(ctx_rows[d], B, P, dec_seg, True, compute_dtype(self.fusion_tokens))
+            else:
+                fp32 = d in fp32_output_adapters
+                rows = rows_of(fp32)
+                with torch.autocast("cuda", enabled=False) if fp32 else contextlib.nullcontext():
+                    tk = adapter.forward_tokens(rows, B, P, dec_seg, once=True)
+            C = adapter.num_channels
+            preds[d] = PredTokens(tk, B, C, H, W, adapter.P_H) if self.fuse_unpatchify_loss else \
+                ops.unpatchify(tk, B, C, H, W, adapter.P_H)
+        return preds
 
     # ---- the hot path ----------------------------------------------------------------------------------------------------
     def forward(self,
@@ -358,54 +457,15 @@ class MultiMAE(nn.Module):
                 sample_tasks_uniformly: bool = False,
                 fp32_output_adapters: List[str] = [],
                 return_token_indices: Optional[Tuple[int]] = None):
-        x = {'s1': x} if isinstance(x, torch.Tensor) else x
-        B, _, H, W = x['s1'].shape                      # KeyError without 's1', as in the reference (:360)
-        device = x['s1'].device
+        x, B, H, W, P, N, T = self._begin(x, 's1', mask_inputs, num_encoded_tokens, return_token_indices)
         doms = self.domains
-        for d in doms:
-            _ = x[d]                                    # every configured modality must be present (:402-407)
-        if exists(return_token_indices):                # reference :478-484
-            assert len(set(return_token_indices)) == len(return_token_indices), 'all indices must be unique'
-            assert all(i < self.max_return_tokens for i in return_token_indices), \
-                'indices must range from 0 to max_num_return_tokens - 1'
-        M, D, Hh, dh = len(doms), self.dim_tokens, self.heads, self.dim_head
-        I = Hh * dh
-        ad0 = self.input_adapters[doms[0]]
-        ps = ad0.P_H
-        nh, nw = H // ps, W // ps
-        P = nh * nw
-        assert P == self.fusion_tokens.shape[1], "fusion tokens are tied to the patch grid (reference :87)"
-        T = compute_dtype(self.fusion_tokens)
-        N = num_encoded_tokens if mask_inputs else M * P
-
-        # -- masks + device-side descriptors (no host sync on the random path) ---------------------------------------------
-        if task_masks is None:
-            placeholders = {d: torch.empty(B, P, 0, device=device) for d in doms}
-            task_masks, ids_keep, ids_restore = self.generate_random_masks(
-                placeholders, N, alphas=alphas, sample_tasks_uniformly=sample_tasks_uniformly)
-            mask_all = torch.cat([task_masks[d][:(B if self.per_sample_masks else 1)] for d in doms], dim=1)
-            explicit = False
-        else:
-            mask_full = torch.cat([task_masks[d] for d in doms], dim=1).to(torch.int64)
-            ids_shuffle = torch.argsort(mask_full, dim=1, stable=True)           # reference :397-399 (outputs unused)
-            ids_restore = torch.argsort(ids_shuffle, dim=1, stable=True)
-            ids_keep = ids_shuffle[:, :N]
-            mask_all = mask_full if self.per_sample_masks else mask_full[:1]      # row 0 drives the batch (:402-406)
-            explicit = True
-        desc, xm, xf, pend, _ = self._encode(x, doms, mask_all, N, explicit)
-        dm, dm_off, df, df_off = pend
+        M, D = len(doms), self.dim_tokens
+        task_masks, desc = self._descriptors(x, doms, N, task_masks, alphas, sample_tasks_uniformly)
+        xm, xf, pend, _ = self._encode(x, doms, desc)
         BN, BP = B * N, B * P
 
-        def one_delta(a, a_off, b, b_off):
-            if a is None:
-                return b, -1, b_off
-            if b is None:
-                return a, a_off, -1
-            assert a is b
-            return a, a_off, b_off
-
         # ---- final norm (:472) -------------------------------------------------------------------------------------------
-        dl, o1, o2 = one_delta(dm, dm_off, df, df_off)
+        dl, o1, o2 = one_delta(*pend)
         # fp32 tokens (returned: ori_tokens / enc_fus) and, under autocast, their bf16 copy for the pool / decoder projections from
         # the same pass over the residual (the copy's gradient then reaches the LayerNorm backward in bf16: no cast either way)
         res = ops.parts_add_ln([xm, xf], dl, [o1, o2], self.norm.gamma, None, out_dtype=torch.float32,
@@ -417,11 +477,11 @@ class MultiMAE(nn.Module):
 
         # ---- attention pooling into the return tokens (:475-497) ---------------------------------------------------------
         ap = self.attn_pool
-        R = self.max_return_tokens
         # pool K/V over every row + (training forward) the context projection of EVERY decoder over the fusion rows: one node,
         # one GEMM for the three proj_context layers (ops._KvCtx).  fp32 output adapters keep their own fp32 projection.
         fused_ctx = FUSED_DECODER_CTX and self.output_adapters is not None and len(self.output_adapters) > 0 and not fp32_output_adapters and \
             all(hasattr(a, 'decode_rows') and a.dim_tokens_enc is not None for a in self.output_adapters.values())
+        ctx_rows = None
         if fused_ctx:
             ads = list(self.output_adapters.values())
             kvp, ctx_all = ops.kv_ctx_projections(tokens_T, BN, BP, ap.to_kv.weight, [a.proj_context.weight for a in ads],
@@ -436,80 +496,35 @@ class MultiMAE(nn.Module):
             # the pooling attention reads, so that kvp's two gradients are merged by a scatter-add instead of a full-size sum
             # (its one consumer below, ops.mha_cross, returns a gradient tensor it allocates itself: fresh_grad)
             kvp, gk = ops.fork_gather_rows(kvp, desc.tok_fus, filt=desc.tok_mod, nfilt=M, fresh_grad=True)   # (B*N, 2I)
-        rq = linear(ops.layernorm(self.return_tokens[0].contiguous(), ap.norm.gamma, out_dtype=T), ap.to_q.weight)
-        a = ops.mha_cross(rq.repeat(B, 1), kvp, Hh, dh, desc.pool_q, desc.enc_seg, ap.scale, empty_mode=0)
-        pooled = linear(a, ap.to_out.weight).float()                                        # (B*R, D)
-        pooled = pooled + self.mlp(ops.layernorm(pooled, self.norm.gamma, out_dtype=T)).float()
-        return_tokens = pooled.reshape(B, R, D)
-        if exists(return_token_indices):                # a row subset of the pooled queries (each query row is independent)
-            return_tokens = return_tokens[:, torch.tensor(list(return_token_indices), dtype=torch.long, device=device)]
+        return_tokens = self._attn_pool(self.return_tokens[0].contiguous(), kvp, desc.pool_q, desc.enc_seg, B, 0,
+                                        return_token_indices)
 
         if self.output_adapters is None:
             full = torch.cat([ori_tokens, enc_fus], dim=1)
             return full, return_tokens, task_masks                                          # :500-501
 
         # ---- per-modality reconstruction decoders on the encoded fusion tokens (:507-527) --------------------------------
-        input_info = self.generate_input_info({d: P for d in doms}, image_size=(H, W))
-        dec_seg = ops.Segments.dense(B, P, device)
+        # fp32 adapters take the final norm's fp32 output itself -- not the bf16 copy widened again
         enc_rows = tokens_T[BN:]
-        preds = {}
-        # The decoders are independent chains of SMALL kernels (B*P rows x 256 columns: a GEMM of 256 tiles, one per CU, no second
-        # wave to hide its tail).  decoder_streams runs them side by side on their own HIP streams (autograd replays each
-        # chain's backward on the stream its forward ran on), joined before the losses.
-        main = torch.cuda.current_stream()
-        use_streams = self.decoder_streams and len(self.output_adapters) > 1 and enc_rows.is_cuda
-        if use_streams:
-            while len(self._dec_streams) < len(self.output_adapters) - 1:
-                self._dec_streams.append(torch.cuda.Stream(device=enc_rows.device))
-        for i, (d, adapter) in enumerate(self.output_adapters.items()):
-            st_ = self._dec_streams[i - 1] if (use_streams and i > 0) else main
-            if st_ is not main:
-                st_.wait_stream(main)
-            with torch.cuda.stream(st_):
-                # fp32 adapters (:518-527) take the final norm's fp32 output itself, as the reference's do (layer_norm leaves an
-                # autocast region in fp32) -- not the bf16 copy widened again
-                rows = tokens[BN:] if d in fp32_output_adapters else enc_rows
-                with torch.autocast("cuda", enabled=False) if d in fp32_output_adapters else _nullctx():
-                    tk = adapter.decode_rows(ctx_rows[d], B, P, dec_seg, True, T) if fused_ctx else \
-                        adapter.forward_tokens(rows, B, P, dec_seg, once=True)
-                if st_ is not main:
-                    (ctx_rows[d] if fused_ctx else rows).record_stream(st_)
-                    tk.record_stream(main)
-            C = adapter.num_channels
-            preds[d] = PredTokens(tk, B, C, H, W, adapter.P_H) if self.fuse_unpatchify_loss else \
-                ops.unpatchify(tk, B, C, H, W, adapter.P_H)
-        if use_streams:
-            for st_ in self._dec_streams[:len(self.output_adapters) - 1]:
-                main.wait_stream(st_)
+        preds = self._decode(B, H, W, lambda fp32: tokens[BN:] if fp32 else enc_rows, fp32_output_adapters, ctx_rows)
 
         if not self.has_contrastive_tokens:
             return (preds, task_masks, return_tokens, ori_tokens, enc_fus)                  # multimae_quadruplet.py:490
         # ---- contrastive return tokens: one query per modality over the fusion tokens at its kept patches (:530-543) -----
         rt = torch.cat([getattr(self, 'return_token_' + d)[0] for d in doms], dim=0).contiguous()   # (M, D)
-        cq = linear(ops.layernorm(rt, ap.norm.gamma, out_dtype=T), ap.to_q.weight)                  # (M, I)
-        a = ops.mha_cross(cq.repeat(B, 1), gk, Hh, dh, desc.ctr_q, desc.ctr_k, ap.scale, empty_mode=1)
-        r = linear(a, ap.to_out.weight).float()                                             # (B*M, D)
-        r = r + self.mlp(ops.layernorm(r, self.norm.gamma, out_dtype=T)).float()
-        r = r.reshape(B, M, D)
+        r = self._attn_pool(rt, gk, desc.ctr_q, desc.ctr_k, B, 1)                                   # (B, M, D)
         rets = [r[:, i:i + 1, :] for i in range(M)]
         return (preds, task_masks, return_tokens, ori_tokens, enc_fus, *rets)               # :545
 
 
-class _nullctx:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *a):
-        return False
-
-
-def _factory(dim_tokens, depth, heads):
+def _factory(cls, dim_tokens, depth, heads):
+    """A preset of the model class `cls` (this file's, the quadruplet's or the S2+DSM one): the reference's factory signature."""
     def build(input_adapters: Dict[str, nn.Module], output_adapters: Optional[Dict[str, nn.Module]], **kwargs):
-        return MultiMAE(input_adapters=input_adapters, output_adapters=output_adapters, dim_tokens=dim_tokens,
-                        depth=depth, dim_head=64, heads=heads, ff_mult=4, norm_layer=LayerNorm, **kwargs)
+        return cls(input_adapters=input_adapters, output_adapters=output_adapters, dim_tokens=dim_tokens,
+                   depth=depth, dim_head=64, heads=heads, ff_mult=4, norm_layer=LayerNorm, **kwargs)
     return build
 
 
-pretrain_multimae_tiny = _factory(192, 12, 3)      # reference :548-563
-pretrain_multimae_base = _factory(768, 12, 8)      # reference :566-581  (inner width 8*64 = 512, not 768)
-pretrain_multimae_large = _factory(1024, 24, 8)    # reference :584-599
+pretrain_multimae_tiny = _factory(MultiMAE, 192, 12, 3)      # reference :548-563
+pretrain_multimae_base = _factory(MultiMAE, 768, 12, 8)      # reference :566-581  (inner width 8*64 = 512, not 768)
+pretrain_multimae_large = _factory(MultiMAE, 1024, 24, 8)    # reference :584-599

@@ -7,6 +7,9 @@ off: no per-layer Block_Fusion (the encoder is the Zorro-masked Block stack over
 mask_embedding, no per-modality contrastive return tokens; forward returns the 5-tuple
 (preds, task_masks, return_tokens, ori_tokens, encoder_fusion_tokens) (:490).  State-dict keys are the reference's
 (tests/test_gpu_quad.py strict-loads a reference-generated state dict).
+
+Owns nothing but the constructor defaults and the preset table: every forward stage, the layer loop included, is
+multimae_crossattn.MultiMAE's with fusion_blocks / contrastive_tokens off.
 """
 from typing import Dict, Optional, Tuple
 
@@ -32,13 +35,6 @@ class MultiMAE(_mc.MultiMAE):
                          fusion_blocks=False, contrastive_tokens=False)
 
 
-def _factory(dim_tokens, depth, heads):
-    def build(input_adapters: Dict[str, nn.Module], output_adapters: Optional[Dict[str, nn.Module]], **kwargs):
-        return MultiMAE(input_adapters=input_adapters, output_adapters=output_adapters, dim_tokens=dim_tokens, depth=depth,
-                        dim_head=64, heads=heads, ff_mult=4, norm_layer=LayerNorm, **kwargs)
-    return build
-
-
-pretrain_multimae_tiny = _factory(384, 12, 8)      # reference :493-514 (the driver's choice, pretrain_mmae_my.py:248)
-pretrain_multimae_base = _factory(768, 12, 8)      # :517-538
-pretrain_multimae_large = _factory(1024, 24, 8)    # :541-560
+pretrain_multimae_tiny = _mc._factory(MultiMAE, 384, 12, 8)      # reference :493-514 (the driver's choice, pretrain_mmae_my.py:248)
+pretrain_multimae_base = _mc._factory(MultiMAE, 768, 12, 8)      # :517-538
+pretrain_multimae_large = _mc._factory(MultiMAE, 1024, 24, 8)    # :541-560

@@ -87,6 +87,52 @@ def test_random_masks_reproduce_through_explicit_masks(g_model):
         assert torch.equal(out[i], again[i]), i
 
 
+@pytest.fixture(scope="module")
+def plain_bf16(g_model):
+    """The bf16 forward of case `both` without options, shared (and left unchanged) by the two option tests below; they reach this
+    model through the pooling and decoder stages it shares with multimae_crossattn.  -> (call(**options), its plain result)."""
+    model = _loaded(g_model)
+    c = Golden("s2dsm_tiny_both.npz")
+    x = {k: v.to(DEV) for k, v in g_model.sub("x").items()}
+    masks = {d: c.t("mask/" + d).to(DEV) for d in DOMS}
+
+    def call(**options):
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            return model(x, task_masks=masks, num_encoded_tokens=int(c.t("N")), **options)
+    return call, call()
+
+
+def _same_but(out, plain, preds=DOMS, others=(2, 3, 4)):
+    for d in preds:
+        assert torch.equal(out[0][d], plain[0][d]), d
+    for i in others:
+        assert torch.equal(out[i], plain[i]), i
+
+
+def test_return_token_indices_select_rows_of_the_pooled_tokens(plain_bf16):
+    """`return_token_indices=(0, 2)`: rows 0 and 2 of the plain call's pooled tokens, exactly; nothing else moves."""
+    call, plain = plain_bf16
+    out = call(return_token_indices=(0, 2))
+    assert plain[2].shape[1] == 3 and out[2].shape[1] == 2
+    assert torch.equal(out[2], plain[2][:, [0, 2]])
+    _same_but(out, plain, others=(3, 4))
+
+
+def test_fp32_output_adapter_agrees_with_its_bf16_run(plain_bf16):
+    """`fp32_output_adapters=['dem']`: the dem decoder leaves the autocast region and reads the fp32 fusion grid, so it differs
+    from its bf16 run by what bf16 costs one decoder -- held to the bound this file holds a bf16 prediction image to against the
+    fp32 reference: 1e-2 relative L2, or 1.5x what bf16 costs the reference's own arithmetic on it.  Everything else: exact."""
+    call, plain = plain_bf16
+    out = call(fp32_output_adapters=["dem"])
+    _same_but(out, plain, preds=("s2",))
+    c, anchor = Golden("s2dsm_tiny_both.npz"), Golden("s2dsm_tiny_bf16.npz").sub("case_both")
+    tol = max(1e-2, 1.5 * parity._l2rel(anchor["pred/dem"].double(), torch.from_numpy(c.z["pred/dem"].copy()).double()))
+    err = parity._l2rel(out[0]["dem"].double(), plain[0]["dem"].double())
+    print("fp32 dem adapter vs bf16 run: rel L2 %.3e (bound %.3e)" % (err, tol))
+    assert out[0]["dem"].dtype == torch.float32 and torch.isfinite(out[0]["dem"]).all()
+    assert 0.0 < err <= tol, (err, tol)
+
+
 def test_per_sample_masks_match_single_sample_runs(g_model):
     """per_sample_masks=True: every sample uses its own mask row (tok_patch is per row) -- the same as running each sample alone."""
     model = _loaded(g_model)

@@ -7,11 +7,19 @@ package object pointing at the reference directory, the canonical downstream zor
 fixture holds arrays, the JSON configuration and the ordered state-dict key list -- no program text.
 
     python tools/make_golden_s2dsm.py            # (re)write the fixture files
-    python tools/make_golden_s2dsm.py --check    # regenerate in memory; exit 1 unless every array is bitwise identical
+    python tools/make_golden_s2dsm.py --check    # regenerate in memory; exit 1 unless the committed files are reproduced
 
-Reproducible by construction: fixed seeds, single-threaded torch (the order of every CPU reduction is then fixed), and .npz
-containers written with a fixed entry timestamp, so the same arrays give the same file bytes.  --check compares the arrays
-(names, dtypes, shapes and raw bytes), which is what the tests read.
+Reproducible by construction: fixed seeds, single-threaded torch (the order of every CPU reduction is then fixed), .npz
+containers written with a fixed entry timestamp, and the host requirement below, so the same arrays give the same file bytes.
+
+Host requirement.  torch's CPU libraries pick their kernels by the host's instruction set, and different kernels round
+differently.  The files were written with MKL on its AVX2 code path and oneDNN without native bf16 / AMX instructions; both are
+pinned here before torch loads (HOST_PINS), which is a no-op on such a host and restores that arithmetic on a newer one:
+  * the model file (seeded initialisation: RNG + MKL vector math) and the bf16-autocast file (its GEMMs and the LSTM run in oneDNN)
+    then regenerate bit for bit also on a host with native bf16 / AMX units, and --check compares them bit for bit;
+  * the two fp32 result files go through MKL's sgemm, whose blocking -- and with it the summation order -- is chosen per CPU
+    vendor and model inside the AVX2 path and cannot be pinned.  They regenerate bit for bit on the host family that wrote them;
+    elsewhere --check holds their float arrays to the fp32 rounding bound of differences(), everything else in them exactly.
 """
 import argparse
 import importlib
@@ -22,8 +30,12 @@ import sys
 import types
 import zipfile
 
-import numpy as np
-import torch
+HOST_PINS = {"MKL_ENABLE_INSTRUCTIONS": "AVX2", "ONEDNN_MAX_CPU_ISA": "AVX512_CORE"}
+for _k, _v in HOST_PINS.items():          # read once, when the libraries load: before `import torch`
+    os.environ[_k] = _v
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -169,8 +181,16 @@ def npz_bytes(bag) -> bytes:
     return buf.getvalue()
 
 
-def differences(committed: bytes, fresh: bytes):
-    """-> list of "name: why" for the arrays that are not bitwise identical (or exist on one side only)."""
+FP32_RESULT_FILES = FILES[1:3]       # the files behind MKL's sgemm (see the module docstring); the other two compare bit for bit
+FP32_RTOL, FP32_ATOL = 1e-5, 1e-7
+
+
+def differences(committed: bytes, fresh: bytes, fp32_rounding: bool = False):
+    """-> list of "name: why" for the arrays that are not bitwise identical (or exist on one side only).
+    fp32_rounding (the two fp32 result files only): a float array also passes when max |difference| <= 1e-5 of its largest
+    magnitude + 1e-7.  1e-5 is 84 fp32 ulps: every value is behind some ten reductions of up to ~1e3 terms, each off by a few
+    ulps between two summation orders, and it is 100x below the 1e-3 at which the tests read these files.  1e-7 is one ulp of the
+    O(1) terms that cancel in Attention_LSTM's bias gradient, which is 0 in exact arithmetic and rounding noise in any run."""
     a, b = np.load(io.BytesIO(committed)), np.load(io.BytesIO(fresh))
     out = ["%s: only in one file" % k for k in sorted(set(a.files) ^ set(b.files))]
     for k in sorted(set(a.files) & set(b.files)):
@@ -178,23 +198,28 @@ def differences(committed: bytes, fresh: bytes):
         if x.dtype != y.dtype or x.shape != y.shape:
             out.append("%s: %s%s vs %s%s" % (k, x.dtype, x.shape, y.dtype, y.shape))
         elif x.tobytes() != y.tobytes():
-            d = np.abs(x.astype(np.float64) - y.astype(np.float64)).max() if x.dtype.kind == "f" else "-"
-            out.append("%s: values differ (max abs %s)" % (k, d))
+            if x.dtype.kind != "f":
+                out.append("%s: values differ" % k)
+                continue
+            d = np.abs(x.astype(np.float64) - y.astype(np.float64)).max()
+            lim = FP32_RTOL * np.abs(x.astype(np.float64)).max() + FP32_ATOL if fp32_rounding else 0.0
+            if not d <= lim:
+                out.append("%s: values differ (max abs %s, allowed %s)" % (k, d, lim))
     return out
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--check", action="store_true", help="regenerate and compare every array bit for bit with the committed fixture")
+    ap.add_argument("--check", action="store_true", help="regenerate and compare every array with the committed fixture (see the module docstring)")
     a = ap.parse_args()
-    torch.set_num_threads(1)          # single-threaded reductions: the fixtures regenerate bit for bit
+    torch.set_num_threads(1)          # single-threaded reductions: a fixed summation order
     data = generate()
     if a.check:
         bad = 0
         for name, b in data.items():
             with open(os.path.join(GOLDEN, name), "rb") as f:
-                diff = differences(f.read(), b)
-            print(name + ":", "identical arrays" if not diff else "DIFFERS: " + "; ".join(diff[:8]))
+                diff = differences(f.read(), b, fp32_rounding=name in FP32_RESULT_FILES)
+            print(name + ":", "reproduced" if not diff else "DIFFERS: " + "; ".join(diff[:8]))
             bad += bool(diff)
         sys.exit(1 if bad else 0)
     for name, b in data.items():
