@@ -28,7 +28,7 @@ extern "C" {
                                 from 4 to 8 floats (mmae_adamw_control / _step_ctl read [4], [5]); + mmae_adamw_tick, mmae_mha_fwd_route.  6: + mmae_pad_copy_bf16_batched
                                 (additive: no existing signature changed).  7: + mmae_mha_bwd_fused, mmae_mha_bwd_fused_supported, mmae_mha_bwd_fused_ws_floats
                                 (additive); later additive entry points keep 7: mmae_trunc_standardize, mmae_bilstm_cell1_fwd / _bwd,
-                                mmae_bilstm_cell2_pool_fwd / _bwd */
+                                mmae_bilstm_cell2_pool_fwd / _bwd, mmae_argmax_confusion, mmae_label_confusion, mmae_confusion_scores */
 int mmae_abi_version(void);
 /* hipError_t of this thread's most recent launch that returned MMAE_ERR_LAUNCH (0: none); reading resets it. */
 int mmae_last_hip_error(void);
@@ -269,6 +269,32 @@ int mmae_stage_tiles(int kind, int in_dtype, int B, int C, int H, int W, int fac
  * mean / stdv: (B) fp32 outputs of mean and sqrt(var + eps), or NULL.  n < 2^31; k_lo >= 0, k_hi <= n, k_hi - k_lo >= 2. */
 int mmae_trunc_standardize(int B, long n, long k_lo, long k_hi, float eps, const float* x, float* y, float* mean, float* stdv,
                            void* stream);
+
+/* ---- segmentation metrics (DS/utils/metrics.py:7-86 ConfMatrix, driven from DS/maskformer_train_seg.py:243-281; the class map of the
+ * pretraining side is preds['dnw'].argmax(1), PT/infer_mmae_my.py:256; DS = downstream/semantic_segmentation) ---------------------
+ * mmae_argmax_confusion: pred is the fp32 logit image (B,C,H,W) or the decoder's token-major output (B*P, C*patch^2) in (c ph pw)
+ * order, fp32 or bf16 -- the two forms of mmae_masked_ce_loss_fwd, same checks (patch % 4 == 0, H and W multiples of patch, image
+ * form fp32 only); target (B,H,W) int64; mask (B,P) int64 {0,1}: only pixels of patches with mask == 1 count (the predicted ones,
+ * as in the losses), NULL: all patches.  Per counted pixel p = argmax_c logit + pred_offset, g = target; the pixel is dropped when
+ * g == ignore_label (negative: ignore nothing) or when g or p lies outside [0, K) (sklearn's confusion_matrix with
+ * labels=arange(K) drops those too); otherwise conf[g*K + p] += 1.  conf: (K,K) int64, ACCUMULATED into (the caller zeroes it),
+ * exact and independent of scheduling (integer atomics).  argmax as torch.argmax on the CPU: lowest index among equal maxima, a
+ * NaN beats every number and the first NaN wins, all -inf gives 0.  1 <= C, 1 <= K <= 128, 0 <= pred_offset, B*H*W < 2^31; pred
+ * and target 16-byte aligned. */
+int mmae_argmax_confusion(int pred_dtype, int pred_is_tokens, int B, int C, int H, int W, int patch, const void* pred,
+                          const long long* target, const long long* mask, int K, int pred_offset, long ignore_label,
+                          long long* conf, void* stream);
+/* the same counting over two flat int64 label arrays of n entries (ConfMatrix.add_batch: argmax taken elsewhere); same dropping
+ * rules.  1 <= n < 2^31, 1 <= K <= 128. */
+int mmae_label_confusion(long n, const long long* gt, const long long* pred, int K, long ignore_label, long long* conf,
+                         void* stream);
+/* scores of a (K,K) int64 matrix into out, 4 + 2K fp64 values, no host synchronisation (row_i / col_i: sums of row / column i):
+ *   out[0] mIoU: mean over ALL K classes of cm[i,i] / (row_i + col_i - cm[i,i]), 0 where that is 0/0 (metrics.py:76-86);
+ *   out[1] AA: sum_i cm[i,i] / row_i (0 where row_i == 0) over the number of rows with row_i > 0, NaN when none (metrics.py:57-66);
+ *   out[2] overall accuracy trace / total, NaN when total == 0 (NOT in the reference: an addition);
+ *   out[3] number of existing classes, rows with row_i > 0 (metrics.py:19-20);
+ *   out[4 .. 4+K) the per-class IoU terms of out[0]; out[4+K .. 4+2K) per-class recall cm[i,i] / row_i (get_sa), 0 where row_i == 0. */
+int mmae_confusion_scores(int K, const long long* conf, double* out, void* stream);
 
 /* ---- two-step BiLSTM fusion + attention pooling (MM/multimae_lstm_s2dsm.py:428-434 with DSI-MM/zorro_utils.py:261-299) ----------
  * Every row j < R is the length-2 sequence (x0_j, x1_j) through nn.LSTM(D, D, bidirectional), h0 = c0 = 0, gates i, f, g, o;

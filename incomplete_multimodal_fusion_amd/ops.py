@@ -1553,6 +1553,93 @@ def trunc_standardize(x: torch.Tensor, lo: float = 0.1, hi: float = 0.9, eps: fl
     return (y, mean, std) if return_stats else y
 
 
+# ------------------------------------------------------------------------------------------------ segmentation metrics
+def _al16(t):
+    """The metric kernels read 16 bytes per lane: a contiguous view that starts off a 16-byte boundary is copied."""
+    t = _c(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _conf_buffer(conf, K: int, dev):
+    if conf is None:
+        return torch.zeros(K, K, dtype=torch.int64, device=dev)
+    if conf.dtype != torch.int64 or tuple(conf.shape) != (K, K) or not conf.is_contiguous():
+        raise ValueError("conf: a contiguous (%d, %d) int64 tensor expected (got %s %s)" % (K, K, tuple(conf.shape), conf.dtype))
+    return conf
+
+
+def argmax_confusion(pred, target, mask, K: int, patch: int, conf: Optional[torch.Tensor] = None, pred_offset: int = 0,
+                     ignore_label: int = -1):
+    """Fused argmax + confusion matrix (utils/metrics.py:7-55 on `preds.argmax(1)`, infer_mmae_my.py:256) in one kernel.
+    pred: the (B,C,H,W) fp32 logit image, a multimae_crossattn.PredTokens, or a (tokens, C) pair -- tokens (B*P, C*patch^2) in
+    (c ph pw) order, fp32 or bf16, as masked_ce_tokens takes them.  target (B,H,W) class ids; mask (B,P) {0,1} or None: only
+    patches with mask == 1 count.  A pixel is dropped when target == ignore_label (negative: none) or when target or
+    argmax + pred_offset lies outside [0, K).  Returns the (K,K) int64 device tensor, rows = target, columns = prediction;
+    with `conf` the counts are ADDED to it in place.  torch.argmax's tie / NaN rule.  Not differentiable; no host sync."""
+    with torch.no_grad():
+        if hasattr(pred, "tokens") and hasattr(pred, "meta"):
+            B, C, H, W, p = pred.meta
+            if p != patch:
+                raise ValueError("argmax_confusion: patch %d, but the PredTokens were built with patch %d" % (patch, p))
+            tok, is_tokens = pred.tokens, True
+        elif isinstance(pred, (tuple, list)):
+            tok, C = pred
+            B, H, W = target.shape
+            is_tokens = True
+        else:
+            if pred.dim() != 4:
+                raise ValueError("argmax_confusion: a (B, C, H, W) logit image expected (got shape %s)" % (tuple(pred.shape),))
+            B, C, H, W = pred.shape
+            tok, is_tokens = pred.float(), False
+        tok = _al16(tok.detach())
+        if tuple(target.shape) != (B, H, W):
+            raise ValueError("argmax_confusion: class-map target must be (B, H, W) = %s (got %s)" % ((B, H, W), tuple(target.shape)))
+        P = (H // patch) * (W // patch) if patch > 0 else 0
+        if is_tokens and tuple(tok.shape) != (B * P, C * patch * patch):
+            raise ValueError("argmax_confusion: tokens must be (B*P, C*patch^2) = %s (got %s)" % ((B * P, C * patch * patch), tuple(tok.shape)))
+        target = _al16(target.detach().to(torch.int64))
+        if mask is not None:
+            mask = _c(mask.detach().to(torch.int64))
+            if mask.numel() != B * P:
+                raise ValueError("argmax_confusion: mask must hold B*P = %d entries (got %s)" % (B * P, tuple(mask.shape)))
+        ptr(tok); ptr(target)                                           # host tensors: refused before anything is allocated
+        conf = _conf_buffer(conf, K, tok.device)
+        call("mmae_argmax_confusion", dt(tok), int(is_tokens), B, C, H, W, patch, ptr(tok), ptr(target), ptr(mask), K,
+             int(pred_offset), int(ignore_label), ptr(conf), stream())
+    return conf
+
+
+def label_confusion(gt, pred, K: int, conf: Optional[torch.Tensor] = None, ignore_label: int = -1):
+    """Confusion matrix of two label tensors of one shape (ConfMatrix.add_batch, utils/metrics.py:22-55, with the argmax taken
+    elsewhere); the dropping rules of argmax_confusion.  Returns the (K,K) int64 device tensor, accumulated in place when `conf`
+    is given.  Not differentiable; no host sync."""
+    with torch.no_grad():
+        if tuple(gt.shape) != tuple(pred.shape):
+            raise ValueError("label_confusion: gt %s and pred %s differ in shape" % (tuple(gt.shape), tuple(pred.shape)))
+        ptr(gt); ptr(pred)
+        gt = _c(gt.detach().to(torch.int64))
+        pred = _c(pred.detach().to(torch.int64))
+        conf = _conf_buffer(conf, K, gt.device)
+        if gt.numel():
+            call("mmae_label_confusion", gt.numel(), ptr(gt), ptr(pred), K, int(ignore_label), ptr(conf), stream())
+    return conf
+
+
+def confusion_scores(conf: torch.Tensor) -> torch.Tensor:
+    """(K,K) int64 confusion matrix -> (4 + 2K,) float64 on the device: [mIoU, AA, overall accuracy, existing classes,
+    IoU per class (K), recall per class (K)], the definitions of utils/metrics.py:57-86 (overall accuracy is an addition);
+    see include/mmae_hip.h.  No host sync."""
+    with torch.no_grad():
+        ptr(conf)
+        if conf.dtype != torch.int64 or conf.dim() != 2 or conf.shape[0] != conf.shape[1]:
+            raise ValueError("confusion_scores: a (K, K) int64 tensor expected (got %s %s)" % (tuple(conf.shape), conf.dtype))
+        conf = _c(conf.detach())
+        K = conf.shape[0]
+        out = torch.empty(4 + 2 * K, dtype=torch.float64, device=conf.device)
+        call("mmae_confusion_scores", K, ptr(conf), ptr(out), stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ mask bookkeeping
 def masks_from_draws(dirichlet, noise, noise_all, N: int):
     """dirichlet (R,M) f32, noise (R,M,P) f32, noise_all (R,M*P) f32 on device ->

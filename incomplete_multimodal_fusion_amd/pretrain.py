@@ -206,6 +206,30 @@ def standardize_depth(tasks_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Te
     return out
 
 
+def evaluate_batch(model, tasks_dict: Dict[str, torch.Tensor], loss_fns=None, conf=None, num_encoded_tokens: Optional[int] = None,
+                   task_masks: Optional[Dict[str, torch.Tensor]] = None, patch_size: int = 16, alphas: float = 1.0,
+                   loss_on_unmasked: bool = False):
+    """One validation forward under torch.no_grad(): the task losses as step_losses computes them (contra='none'), and, for every
+    task whose loss is a MaskedCrossEntropyLoss and that has an entry in `conf` ({task: metrics.ConfMatrix}), the confusion counts
+    of the argmax of its logits over the patches that were predicted (mask == 1) -- what the reference asks of its class-map
+    modality (infer_mmae_my.py:256, scored with utils/metrics.py ConfMatrix as maskformer_train_seg.py:243-281 does).  The model
+    is used exactly as PretrainStep.__call__ uses it: drawn masks (num_encoded_tokens, alphas) or explicit task_masks; autocast and
+    model.fuse_unpatchify_loss are the caller's.  No target class is ignored (ignore_label=-1).  Returns (task_losses, masks);
+    no host synchronisation."""
+    in_domains = tuple(model.domains)
+    with torch.no_grad():
+        x = {t: v for t, v in tasks_dict.items() if t in in_domains}
+        out = model(x, task_masks=task_masks, num_encoded_tokens=num_encoded_tokens, alphas=alphas)
+        preds, masks = out[0], out[1]
+        loss_fns = loss_fns or make_loss_fns(tuple(preds.keys()), patch_size)
+        task_losses, _, _ = step_losses(out, tasks_dict, masks, patch_size, loss_fns, contra='none',
+                                        loss_on_unmasked=loss_on_unmasked)
+        for task in preds:
+            if conf is not None and task in conf and isinstance(loss_fns[task], MaskedCrossEntropyLoss):
+                conf[task].add_logits(preds[task], tasks_dict[task], mask=masks[task], ignore_label=-1)
+    return task_losses, masks
+
+
 class PretrainStep:
     """One optimizer step on a batch of tiles already resident on the device.  No host synchronisation.
 
