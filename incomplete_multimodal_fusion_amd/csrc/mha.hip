@@ -438,6 +438,9 @@ template <typename T, int DH> static int launch_bwd(MhaDesc d, int max_q_tiles, 
 
 static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// the kernel variants of the internal test ABI (table in mmae_internal.h): every other number is an argument error
+static bool variant_known(int v) { return v == -1 || v == 0 || v == 2 || v == 4 || v == 5 || v == 23 || v == 50 || v == 55; }
+
 static int check_common(int dtype, int head_dim, int B, int H, int nseg, const void* q, const void* k, const void* v,
                         long qs, long ks, long vs, const int* a, const int* b2, const int* c, const int* d) {
     if (dtype != MMAE_F32 && dtype != MMAE_BF16) return MMAE_ERR_ARG;
@@ -465,6 +468,7 @@ extern "C" int mmae_mha_fwd_variant(int dtype, int head_dim, int B, int H, int n
     d.stat_stride = q_rows_total; d.B = B; d.H = H; d.nseg = nseg; d.max_tiles = max_q_rows / 64 + nseg; d.max_q_rows = max_q_rows; d.max_k_rows = max_k_rows;
     d.scale = scale; d.empty_mode = empty_mode;
     if (variant > 0) { d.hpb_req = (variant >> 8) & 15; variant &= 255; }
+    if (!variant_known(variant)) return MMAE_ERR_ARG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (dtype == MMAE_BF16) return variant < 0 ? (head_dim == 64 ? launch_fwd<bf16, 64>(d, st) : launch_fwd<bf16, 32>(d, st)) : mha_bf16_fwd(d, head_dim, variant, st);
     return head_dim == 64 ? launch_fwd<float, 64>(d, st) : launch_fwd<float, 32>(d, st);
@@ -529,8 +533,9 @@ extern "C" int mmae_mha_bwd_variant(int dtype, int head_dim, int B, int H, int n
     d.stat_stride = q_rows_total; d.B = B; d.H = H; d.nseg = nseg; d.max_q_rows = max_q_rows; d.max_k_rows = max_k_rows;
     d.scale = scale; d.empty_mode = empty_mode;
     if (variant > 0) { d.hpb_req = (variant >> 8) & 15; variant &= 255; }
+    if (!variant_known(variant)) return MMAE_ERR_ARG;
     const int mq = max_q_rows / 64 + nseg, mk = max_k_rows / 64 + nseg;
-    if (variant >= 50 && variant <= 55) {          // fused backward (mha_sh_bwd_kernel): the workspace continues behind the three planes -- mmae_mha_bwd_fused_ws_floats
+    if (variant == 50 || variant == 55) {         // fused backward (mha_sh_bwd_kernel): the workspace continues behind the three planes -- mmae_mha_bwd_fused_ws_floats
         d.dq_ws = delta_ws + 3L * H * q_rows_total;
         d.max_qt = mq;
     }

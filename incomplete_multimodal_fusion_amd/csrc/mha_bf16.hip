@@ -178,10 +178,10 @@ __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlan
 // QB = 16-query blocks per wave: with QB = 2 a block covers 128 queries with the same 4 waves, so every K/V tile that is
 // fetched (L2/HBM) and every K/V fragment read from LDS feeds twice the MFMAs -- the kernel is bound by exactly those two
 // streams (K/V tiles are re-read once per query tile: 1.7 GB per launch at the bench shape), not by issue slots.
-template <int DH, int NW, int QB = 1>
-__global__ __launch_bounds__(NW * 64, 2) void mha_bf16_fwd_kernel(MhaDesc p) {
-    typedef Geo<DH, NW * 64> G;
-    constexpr int NT = NW * 64, BM = NW * 16 * QB;
+template <int DH, int QB = 1>
+__global__ __launch_bounds__(256, 2) void mha_bf16_fwd_kernel(MhaDesc p) {
+    typedef Geo<DH> G;
+    constexpr int NT = 256, BM = 64 * QB;
     __shared__ __attribute__((aligned(16))) bf16 Ks[64 * G::KP];
     __shared__ __attribute__((aligned(16))) bf16 Vs[64 * G::KP];
     __shared__ int tl_row[MAXT], tl_n[MAXT], tl_cnt;
@@ -354,7 +354,9 @@ __global__ __launch_bounds__(NW * 64, 2) void mha_bf16_fwd_kernel(MhaDesc p) {
 // ------------------------------------------------------------------------------------------------------ backward: dQ (+ delta)
 // No per-element masks: rows of a ragged tile beyond its length are ZERO in the LDS images, so a padded key has K = V = 0
 // and contributes K^T dS = 0 to dQ whatever its (finite) dS is.
-// QB = 16-query blocks per wave (see the forward kernel): 2 -> 128-query tiles, K/V tile fetches and fragment reads halve.
+// QB = 16-query blocks per wave (see the forward kernel): 2 -> 128-query tiles, K/V tile fetches and fragment reads halve
+// (measured +-1 %, 207 VGPRs: not built).  Only QB 1 is instantiated; the parameter stays because the same body written
+// without the one-element arrays comes out of hipcc with a different register allocation.
 template <int DH, int QB = 1>
 __global__ __launch_bounds__(256, 2) void mha_bf16_bwd_dq_kernel(MhaDesc p) {
     typedef Geo<DH> G;
@@ -772,8 +774,8 @@ __global__ __launch_bounds__(256, 2) void mha_bf16_bwd_dkdv_kernel(MhaDesc p) {
 }
 
 // ------------------------------------------------------------------------------------------------------ forward, 32x32x16
-// Second-generation forward for head_dim 64 (what mmae_mha_fwd runs; the 16x16x32 kernel above stays as variant 1 / 8 and
-// serves head_dim 32).  What changes against mha_bf16_fwd_kernel:
+// Second-generation forward for head_dim 64 (what mmae_mha_fwd runs where the sample-head kernel does not apply; the 16x16x32
+// kernel above stays as variant 2 and serves head_dim 32).  What changes against mha_bf16_fwd_kernel:
 //   * v_mfma_f32_32x32x16_bf16 with the score tile computed transposed (S^T = K Q^T): a lane owns ONE query and 16 keys of
 //     each 32-key block, so the row maximum is an in-lane max3 chain plus one v_permlane32_swap, and the exponentiated
 //     accumulator registers 8s..8s+7 ARE the B operand of O^T += V^T P^T for k-step s (k-slot permutation absorbed by the
@@ -792,7 +794,7 @@ __global__ __launch_bounds__(256, 2) void mha_bf16_bwd_dkdv_kernel(MhaDesc p) {
 //     column blocks of one transposed read land on the four 64-byte quarters of the 256-byte bank row): SQ_LDS_BANK_CONFLICT 0.
 // Measured (tools/bench_attn.py, one process, B 256): 233-248 us against 240-262 us of the 16x16x32 kernel on the same box
 // (+3...+10 %).  Per-instruction counts fell by 2x (116 VALU + 16 MFMA per 32 x 64 score tile against 192 + 32), time did
-// not follow: the stamped build (variant 9, tools/probes/attn_stamps.py) shows a wave spending 10-11k cycles between its first
+// not follow: a build with per-wave clock stamps showed a wave spending 10-11k cycles between its first
 // instruction and its first key tile -- ~2.8k until the segment table is in registers, ~6k until its (HBM-cold) Q rows and
 // first K/V tile have arrived, ~2k for the LDS staging and two barriers -- against ~2.8k cycles per key-tile iteration and 5
 // iterations per wave on average: block start-up latency, not the inner loop, bounds all three attention kernels at this
@@ -851,39 +853,8 @@ template <int PITCH> struct Stage64 {
 
 #define FWD32_THR 6.0f    // log2 domain: P <= 2^6 between rescales
 
-// Diagnostic build (STAMP; variant 9 of mmae_internal.h, never the product path): per-wave s_memtime sums of where the time
-// goes -- [0] whole key loop, [1] inside the end-of-tile barrier, [2] in the register -> LDS staging block (its vmcnt wait),
-// [3] iterations, [4] kernel entry -> first iteration, [5] 1 per wave with work, [6] entry -> segment table in registers,
-// [7] -> Q rows and first K/V tile arrived.  One row per wave, plain stores (same-address atomics of 41k waves serialise for
-// milliseconds and distort everything they time); mmae_debug_mha_stamps() sums and clears them.
-#ifndef MMAE_DIAG
-#define MMAE_DIAG 1
-#endif
-#define STAMP_WAVES (MMAE_DIAG ? 131072 : 1)
-__device__ unsigned long long g_mha_stamps[STAMP_WAVES][8];
-__device__ __forceinline__ unsigned long long stamp_now() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    return t;
-}
-extern "C" int mmae_debug_mha_stamps(unsigned long long* host8) {
-    if (!host8 || !MMAE_DIAG) return MMAE_ERR_ARG;
-    static unsigned long long* h = nullptr;
-    if (!h) h = new unsigned long long[(size_t)STAMP_WAVES * 8];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_mha_stamps), sizeof(unsigned long long) * STAMP_WAVES * 8) != hipSuccess) return MMAE_ERR_LAUNCH;
-    for (int i = 0; i < 8; ++i) host8[i] = 0;
-    for (size_t w = 0; w < STAMP_WAVES; ++w)
-        for (int i = 0; i < 8; ++i) host8[i] += h[w * 8 + i];
-    void* dptr = nullptr;
-    if (hipGetSymbolAddress(&dptr, HIP_SYMBOL(g_mha_stamps)) != hipSuccess) return MMAE_ERR_LAUNCH;
-    if (hipMemset(dptr, 0, sizeof(unsigned long long) * STAMP_WAVES * 8) != hipSuccess) return MMAE_ERR_LAUNCH;
-    return MMAE_OK;
-}
-
-template <int QB, bool STAMP = false>
+template <int QB>
 __global__ __launch_bounds__(256, 2) void mha_bf16_fwd32_kernel(MhaDesc p) {
-    unsigned long long t_entry = 0, t_seg = 0, t_q = 0, t_loop = 0, t_bar = 0, t_stage = 0;
-    if (STAMP) t_entry = stamp_now();
     constexpr int DH = 64, BM = 128 * QB, KP = 72, VP = 96;
     __shared__ __attribute__((aligned(16))) bf16 Ks[2][64 * KP];
     __shared__ __attribute__((aligned(16))) bf16 Vs[2][64 * VP];
@@ -897,7 +868,6 @@ __global__ __launch_bounds__(256, 2) void mha_bf16_fwd32_kernel(MhaDesc p) {
     const TileSel ts = pick_tile<BM>([&](int s) { return st.ql(s); }, p.nseg, bs.t);
     if (ts.seg < 0) return;
     const long qrow0 = (long)st.qs(ts.seg) + ts.t0;
-    if (STAMP) { __builtin_amdgcn_sched_barrier(0); t_seg = stamp_now(); __builtin_amdgcn_sched_barrier(0); }
     const KeyPlan kp = key_plan(ts.seg, p.nseg, st.kl(ts.seg), p.empty_mode);
     int first_row = 0, first_n = 0;                               // tile 0, known to every wave without the shared list
     if (wave == 0) {
@@ -954,7 +924,6 @@ __global__ __launch_bounds__(256, 2) void mha_bf16_fwd32_kernel(MhaDesc p) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) oacc[qb][d][i] = 0.f;
     }
-    if (STAMP) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); t_q = stamp_now(); __builtin_amdgcn_sched_barrier(0); }
     __syncthreads();                                               // tile list visible
     const int ntile = uni(tl_cnt);
     if (ntile > 0) {
@@ -970,7 +939,6 @@ __global__ __launch_bounds__(256, 2) void mha_bf16_fwd32_kernel(MhaDesc p) {
     const bf16* kbase = Ks[0] + r * KP + 8 * hh;
     bf16x8 qone = z8();
     if (hh == 0) qone[0] = (bf16)1.0f;
-    if (STAMP) t_loop = stamp_now();
     for (int t = 0; t < ntile; ++t) {
         const int cur = t & 1;
         const int kn = uni(tl_n[t]);
@@ -1038,11 +1006,8 @@ __global__ __launch_bounds__(256, 2) void mha_bf16_fwd32_kernel(MhaDesc p) {
         }
         // ---- the next tile's registers go to the idle buffer; the write latency hides under the PV products
         if (t + 1 < ntile) {
-            unsigned long long a = 0;
-            if (STAMP) { __builtin_amdgcn_sched_barrier(0); a = stamp_now(); __builtin_amdgcn_sched_barrier(0); }
             ixk.store(Ks[cur ^ 1], kreg);
             ixv.store(Vs[cur ^ 1], vreg);
-            if (STAMP) { __builtin_amdgcn_sched_barrier(0); t_stage += stamp_now() - a; __builtin_amdgcn_sched_barrier(0); }
         }
         // ---- O^T += V^T P^T : 2 key blocks x 2 k-steps x 2 dh blocks
 #pragma unroll
@@ -1055,28 +1020,11 @@ __global__ __launch_bounds__(256, 2) void mha_bf16_fwd32_kernel(MhaDesc p) {
 #pragma unroll
                     for (int qb = 0; qb < QB; ++qb) oacc[qb][d] = mma32(vfr, pb[qb][kb][s2], oacc[qb][d]);
                 }
-        if (STAMP) {
-            __builtin_amdgcn_sched_barrier(0);
-            const unsigned long long a = stamp_now();
-            __syncthreads();
-            t_bar += stamp_now() - a;
-            __builtin_amdgcn_sched_barrier(0);
-        } else {
-            __syncthreads();
-        }
+        __syncthreads();
         if (t + 2 < ntile) {
             const long r2 = uni(tl_row[t + 2]); const int n2 = uni(tl_n[t + 2]);
             ixk.load(kg + r2 * p.k_stride, n2, kreg);
             ixv.load(vg + r2 * p.v_stride, n2, vreg);
-        }
-    }
-    if (STAMP) {
-        const unsigned long long t_end = stamp_now();
-        const unsigned w = blockIdx.x * 4 + wave;
-        if (lane == 0 && w < STAMP_WAVES) {
-            g_mha_stamps[w][0] = t_end - t_loop; g_mha_stamps[w][1] = t_bar; g_mha_stamps[w][2] = t_stage;
-            g_mha_stamps[w][3] = (unsigned long long)ntile; g_mha_stamps[w][4] = t_loop - t_entry; g_mha_stamps[w][5] = 1ull;
-            g_mha_stamps[w][6] = t_seg - t_entry; g_mha_stamps[w][7] = t_q - t_seg;
         }
     }
 #pragma unroll
@@ -1100,81 +1048,56 @@ __global__ __launch_bounds__(256, 2) void mha_bf16_fwd32_kernel(MhaDesc p) {
 }
 
 // ------------------------------------------------------------------------------------------------------ host side
-// `variant` (per call; mmae_internal.h): forward tiling 0 default, 1, 8; backward 2 -- tools/bench_attn.py A/B material.
-int mha_bf16_fwd(const MhaDesc& d, int head_dim, int g_variant, hipStream_t st) {
-    if (g_variant == 23 || (g_variant >= 50 && g_variant <= 55)) g_variant = 0;   // backward-only variants (head-looping dQ, fused backward): default forward
+// `variant` (per call): one of the numbers of the table in mmae_internal.h; the entry points of mha.hip reject every other one.
+int mha_bf16_fwd(const MhaDesc& d, int head_dim, int variant, hipStream_t st) {
     if (d.max_tiles > MAXT) return MMAE_ERR_ARG;
-    if (head_dim == 64 && g_variant >= 30 && g_variant <= 32) return mha_sh_fwd(d, g_variant - 20, st);   // two tiles per barrier (+ its diagnostics)
-    if (head_dim == 64 && g_variant == 35) return mha_sh_fwd(d, 10, st);
-    if (head_dim == 64 && g_variant == 45) return mha_sh_fwd(d, 4, st);   // diagnostic: sixteen global waves (wrong modality rows)
-    if (head_dim == 64 && (g_variant == 40 || g_variant == 41)) return mha_sh_fwd(d, g_variant - 20, st);   // four loader waves (+ stream only)
-    if (head_dim == 64 && g_variant >= 5 && g_variant <= 8) return mha_sh_fwd(d, g_variant - 5, st);   // sample-head forward (mha_sh.hip); 6 / 7 / 8: diagnostics
-    // default: the sample-head kernel wherever a sample has enough query rows to fill its 16 waves (encoder blocks); the
-    // tile-per-block kernel below for the few-query calls (attention pooling, contrastive pools: 1-8 queries per sample)
-    if (head_dim == 64 && g_variant == 0 && mha_sh_applicable(d)) return mha_sh_fwd(d, 0, st);
-    if (head_dim == 64 && (g_variant == 0 || g_variant == 3 || g_variant == 4 || g_variant == 9)) {
-        // default (0 == 3): 32x32x16 forward, 4 waves x 32 queries = 128-query tiles; 4: 256-query tiles; 9: stamped diagnostic
-        MhaDesc e = d;
-        e.max_tiles = g_variant == 4 ? (d.max_tiles + 3) / 4 + d.nseg : (d.max_tiles + 1) / 2 + d.nseg;
-        const dim3 grid(xcd_grid(e.B, e.H, e.max_tiles)), blk(256);
-        if (g_variant == 4) MMAE_LAUNCH((mha_bf16_fwd32_kernel<2>), grid, blk, 0, st, e);
-        else if (g_variant == 9) {
-#if MMAE_DIAG
-            MMAE_LAUNCH((mha_bf16_fwd32_kernel<1, true>), grid, blk, 0, st, e);
-#else
-            return MMAE_ERR_ARG;
-#endif
-        }
-        else MMAE_LAUNCH((mha_bf16_fwd32_kernel<1>), grid, blk, 0, st, e);
-    } else if (head_dim == 64 && g_variant == 2) {           // round-1 kernel: 16x16x32, 4 waves x 32 queries = 128-query tiles
-        MhaDesc e = d; e.max_tiles = (d.max_tiles + 1) / 2 + d.nseg;
-        MMAE_LAUNCH((mha_bf16_fwd_kernel<64, 4, 2>), dim3(xcd_grid(e.B, e.H, e.max_tiles)), dim3(256), 0, st, e);
-    } else if (head_dim == 64 && g_variant == 18) {          // 8 waves x 16 queries (measured: no gain over 4 x 16)
-        MhaDesc e = d; e.max_tiles = (d.max_tiles + 1) / 2 + d.nseg;
-        MMAE_LAUNCH((mha_bf16_fwd_kernel<64, 8>), dim3(xcd_grid(e.B, e.H, e.max_tiles)), dim3(512), 0, st, e);
-    } else {                                                 // variant 1 (dh 64) / dh 32: 16x16x32, 4 waves x 16 queries
-        dim3 grid(xcd_grid(d.B, d.H, d.max_tiles));
-        if (head_dim == 64) MMAE_LAUNCH((mha_bf16_fwd_kernel<64, 4>), grid, dim3(256), 0, st, d);
-        else MMAE_LAUNCH((mha_bf16_fwd_kernel<32, 4>), grid, dim3(256), 0, st, d);
+    if (head_dim != 64) {                                    // dh 32: 16x16x32, 4 waves x 16 queries, whatever the variant
+        MMAE_LAUNCH((mha_bf16_fwd_kernel<32>), dim3(xcd_grid(d.B, d.H, d.max_tiles)), dim3(256), 0, st, d);
+        MMAE_CHECK_LAUNCH();
+        return MMAE_OK;
     }
+    // the sample-head kernel (mha_sh.hip) on request (5), and by default (0 and the backward-only 23 / 50 / 55) wherever a sample has
+    // enough query rows to fill its 16 waves (encoder blocks); the tile-per-block kernels below for the few-query calls (attention
+    // pooling, contrastive pools: 1-8 queries per sample)
+    if (variant == 5 || (variant != 2 && variant != 4 && mha_sh_applicable(d))) return mha_sh_fwd(d, st);
+    MhaDesc e = d;                                           // 4 waves x 32 queries = 128-query tiles; variant 4: 256-query tiles
+    e.max_tiles = variant == 4 ? (d.max_tiles + 3) / 4 + d.nseg : (d.max_tiles + 1) / 2 + d.nseg;
+    const dim3 grid(xcd_grid(e.B, e.H, e.max_tiles)), blk(256);
+    if (variant == 2) MMAE_LAUNCH((mha_bf16_fwd_kernel<64, 2>), grid, blk, 0, st, e);      // round-1 kernel: 16x16x32
+    else if (variant == 4) MMAE_LAUNCH((mha_bf16_fwd32_kernel<2>), grid, blk, 0, st, e);
+    else MMAE_LAUNCH((mha_bf16_fwd32_kernel<1>), grid, blk, 0, st, e);                     // default: 32x32x16
     MMAE_CHECK_LAUNCH();
     return MMAE_OK;
 }
 
-int mha_bf16_bwd(MhaDesc d, int head_dim, int max_q_tiles, int max_k_tiles, int g_variant, hipStream_t st) {
+int mha_bf16_bwd(MhaDesc d, int head_dim, int max_q_tiles, int max_k_tiles, int variant, hipStream_t st) {
     if (max_q_tiles > MAXT || max_k_tiles > MAXT) return MMAE_ERR_ARG;
-    if ((g_variant >= 30 && g_variant <= 32) || g_variant == 40 || g_variant == 41 || g_variant == 45) g_variant = 0;   // forward-only variants: default backward
-    if (g_variant == 35) g_variant = 5;                      // two-tile forward + sample-head dQ
+    const bool dh64 = head_dim == 64;
     d.max_tiles = max_q_tiles;
-    if (g_variant >= 50 && g_variant <= 55) {                // dQ + dK + dV in ONE key-stationary kernel (mha_sh.hip: mha_sh_bwd_kernel); 51..55: its diagnostics
-        if (head_dim == 64 && mha_sh_fused_supported(d)) return mha_sh_bwd_fused(d, g_variant - 50, st);
-        g_variant = 0;                                       // shapes beyond its schedule tables: the product pair
+    if (variant == 50 || variant == 55) {                    // dQ + dK + dV in ONE key-stationary kernel (mha_sh.hip: mha_sh_bwd_kernel)
+        if (dh64 && mha_sh_fused_supported(d)) return mha_sh_bwd_fused(d, variant == 55, st);
+        variant = 0;                                         // shapes beyond its schedule tables: the product pair
     }
     // dQ: the tile-per-block kernel stays the default.  The query-stationary sample-head kernel (mha_sh.hip: mha_sh_dq_kernel) runs
     // on request only (variant 5: tests, tools/bench_attn.py): its 8 KB of operand staging per wave cap it at 12 waves, i.e. 128 local
     // query rows per pass, and the usual Dirichlet splits keep more than 128 tokens of some modality -- a second pass.  Measured at
     // the bench shape: 349 against 378 us with equal splits, but 30 us SLOWER than this kernel at 201 / 64 / 119.
-    const bool sh_dq = head_dim == 64 && mha_sh_dq_supported(d) && (g_variant == 5 || g_variant == 6 || g_variant == 7);
-    if (sh_dq) {
-        const int rc = mha_sh_dq(d, (g_variant == 6 || g_variant == 7) ? g_variant - 5 : 0, st);
+    const dim3 qgrid(xcd_grid(d.B, d.H, max_q_tiles)), blk(256);
+    if (dh64 && variant == 5 && mha_sh_dq_supported(d)) {
+        const int rc = mha_sh_dq(d, st);
         if (rc != MMAE_OK) return rc;
-    } else
-    if (head_dim == 64 && g_variant == 23) {                 // head-looping blocks: (sample, tile) grid, prefetch across heads
-        MMAE_LAUNCH((mha_bf16_bwd_dq_heads_kernel<64>), dim3(xcd_grid(d.B, 1, max_q_tiles)), dim3(256), 0, st, d);
-    } else
-    if (head_dim == 64 && g_variant == 22) {                 // 128-query tiles: measured +-1 % (207 VGPRs, 2 waves/SIMD) -> not default
-        d.max_tiles = (max_q_tiles + 1) / 2 + d.nseg;
-        MMAE_LAUNCH((mha_bf16_bwd_dq_kernel<64, 2>), dim3(xcd_grid(d.B, d.H, d.max_tiles)), dim3(256), 0, st, d);
-    } else if (head_dim == 64) MMAE_LAUNCH((mha_bf16_bwd_dq_kernel<64>), dim3(xcd_grid(d.B, d.H, max_q_tiles)), dim3(256), 0, st, d);
-    else MMAE_LAUNCH((mha_bf16_bwd_dq_kernel<32>), dim3(xcd_grid(d.B, d.H, max_q_tiles)), dim3(256), 0, st, d);
+    } else if (dh64 && variant == 23) {                      // head-looping blocks: (sample, tile) grid, prefetch across heads
+        MMAE_LAUNCH((mha_bf16_bwd_dq_heads_kernel<64>), dim3(xcd_grid(d.B, 1, max_q_tiles)), blk, 0, st, d);
+    } else if (dh64) MMAE_LAUNCH((mha_bf16_bwd_dq_kernel<64>), qgrid, blk, 0, st, d);
+    else MMAE_LAUNCH((mha_bf16_bwd_dq_kernel<32>), qgrid, blk, 0, st, d);
     MMAE_CHECK_LAUNCH();
     d.max_tiles = max_k_tiles;
     // dK / dV: the key-stationary sample-head kernel (mha_sh.hip) where a sample has enough keys to fill it (encoder blocks) or
-    // when asked for (variant 5: tests); variant 3 = the tile-per-block kernels of round 2 throughout
-    if (head_dim == 64 && mha_sh_dkdv_supported(d) && (g_variant == 5 || ((g_variant == 0 || g_variant == 23) && d.max_k_rows >= 128))) return mha_sh_dkdv(d, 0, st);
-    if (head_dim == 64 && mha_sh_dkdv_supported(d) && (g_variant == 6 || g_variant == 7)) return mha_sh_dkdv(d, g_variant - 5, st);   // diagnostics: stream only / no ring DMA
-    if (head_dim == 64) MMAE_LAUNCH((mha_bf16_bwd_dkdv_kernel<64>), dim3(xcd_grid(d.B, d.H, max_k_tiles)), dim3(256), 0, st, d);
-    else MMAE_LAUNCH((mha_bf16_bwd_dkdv_kernel<32>), dim3(xcd_grid(d.B, d.H, max_k_tiles)), dim3(256), 0, st, d);
+    // when asked for (variant 5: tests); variants 2 / 4: the tile-per-block kernel throughout
+    if (dh64 && mha_sh_dkdv_supported(d) && (variant == 5 || ((variant == 0 || variant == 23) && d.max_k_rows >= 128))) return mha_sh_dkdv(d, st);
+    const dim3 kgrid(xcd_grid(d.B, d.H, max_k_tiles));
+    if (dh64) MMAE_LAUNCH((mha_bf16_bwd_dkdv_kernel<64>), kgrid, blk, 0, st, d);
+    else MMAE_LAUNCH((mha_bf16_bwd_dkdv_kernel<32>), kgrid, blk, 0, st, d);
     MMAE_CHECK_LAUNCH();
     return MMAE_OK;
 }

@@ -60,10 +60,10 @@ int mha_bf16_fwd(const MhaDesc& d, int head_dim, int variant, hipStream_t st);
 int mha_bf16_bwd(MhaDesc d, int head_dim, int max_q_tiles, int max_k_tiles, int variant, hipStream_t st);
 // sample-head kernels (mha_sh.hip): bf16, head_dim 64; d.max_tiles = key tiles per sample (upper bound)
 bool mha_sh_applicable(const MhaDesc& d);
-int mha_sh_fwd(const MhaDesc& d, int mode, hipStream_t st);
+int mha_sh_fwd(const MhaDesc& d, hipStream_t st);
 bool mha_sh_dkdv_supported(const MhaDesc& d);
 bool mha_sh_dq_supported(const MhaDesc& d);
-int mha_sh_dq(const MhaDesc& d, int mode, hipStream_t st);
+int mha_sh_dq(const MhaDesc& d, hipStream_t st);
 bool mha_sh_fused_supported(const MhaDesc& d);
-int mha_sh_bwd_fused(const MhaDesc& d, int mode, hipStream_t st);   // dQ + dK + dV in one kernel (+ the row-constant pre-pass); needs d.dq_ws; mode 1..3: diagnostics
-int mha_sh_dkdv(const MhaDesc& d, int mode, hipStream_t st);   // needs workspace planes 1, 2 (see mha_bf16_bwd_dq_kernel)   // mode 0: product; 1 / 2: stream-only / compute-only diagnostics
+int mha_sh_bwd_fused(const MhaDesc& d, bool rc, hipStream_t st);   // dQ + dK + dV in one kernel; needs d.dq_ws; rc: row constants in the kernel instead of the pre-pass
+int mha_sh_dkdv(const MhaDesc& d, hipStream_t st);   // needs workspace planes 1, 2 (see mha_bf16_bwd_dq_kernel)

@@ -34,12 +34,6 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 #define LDS_AS __attribute__((address_space(3)))
 
-#ifndef SH_SKEW
-#define SH_SKEW 0
-#endif
-#ifndef SH_SLEEP_CLASS
-#define SH_SLEEP_CLASS (-1)
-#endif
 #define SH_NS 4                 // ring stages
 #define SH_D 3                  // tiles in flight ahead of the consumer
 #define SH_MAXT 64              // key tiles per sample (one lane each)
@@ -194,36 +188,6 @@ struct ShSlot {
     int nq;               // valid queries of the slot (wave-uniform): lane pair r is live iff r < nq
 };
 
-// Diagnostic build (MODE 3; never the product path): per-wave s_memtime sums of where an iteration goes.  One row per wave,
-// plain stores; mmae_debug_sh_stamps() sums the rows of the two roles separately and clears them.
-//   [0] vmcnt wait at the top  [1] barrier  [2] ring issue + tile record  [3] slot switch  [4] QK^T  [5] softmax  [6] PV
-//   [7] finish (stores)  [8] whole loop  [9] units (slot-steps)  [10] iterations  [11] waves
-//   slot switch in detail: [12] wait for the staged Q  [13] LDS reads + conversion  [14] next-target scan  (the rest of [3] is the Q DMA issue)
-#ifndef MMAE_DIAG
-#define MMAE_DIAG 1
-#endif
-#define SH_STAMP_WAVES (MMAE_DIAG ? 8192 : 1)
-__device__ unsigned long long g_sh_stamps[SH_STAMP_WAVES][16];
-__device__ __forceinline__ unsigned long long sh_now() {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    return t;
-}
-extern "C" int mmae_debug_sh_stamps(unsigned long long* host32) {
-    if (!host32 || !MMAE_DIAG) return MMAE_ERR_ARG;
-    static unsigned long long* h = nullptr;
-    if (!h) h = new unsigned long long[(size_t)SH_STAMP_WAVES * 16];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_sh_stamps), sizeof(unsigned long long) * SH_STAMP_WAVES * 16) != hipSuccess) return MMAE_ERR_LAUNCH;
-    for (int i = 0; i < 32; ++i) host32[i] = 0;
-    for (size_t w = 0; w < SH_STAMP_WAVES; ++w)
-        for (int i = 0; i < 16; ++i) host32[16 * ((w & 15) >= 8) + i] += h[w * 16 + i];      // [0..15] global waves, [16..31] local waves
-    void* dptr = nullptr;
-    if (hipGetSymbolAddress(&dptr, HIP_SYMBOL(g_sh_stamps)) != hipSuccess) return MMAE_ERR_LAUNCH;
-    if (hipMemset(dptr, 0, sizeof(unsigned long long) * SH_STAMP_WAVES * 16) != hipSuccess) return MMAE_ERR_LAUNCH;
-    return MMAE_OK;
-}
-#define SH_T(i) do { if (ST) { __builtin_amdgcn_sched_barrier(0); const unsigned long long n__ = sh_now(); tt[i] += n__ - tl; tl = n__; __builtin_amdgcn_sched_barrier(0); } } while (0)
-
 // scores of 64 keys x 32 queries, online softmax, O^T += V^T P^T
 template <bool ST>
 __device__ __forceinline__ void sh_attend(ShSlot& s, bool fresh, const bf16* Kst, const bf16* Vst, int stage_el, const ShAddr& ad,
@@ -245,8 +209,6 @@ __device__ __forceinline__ void sh_attend(ShSlot& s, bool fresh, const bf16* Kst
         __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);        // emitted order: 4 LDS reads, then the 5 products
         __builtin_amdgcn_sched_group_barrier(0x008, 5, 0);
     }
-    if (ST) asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");    // let the MFMA chain drain into [4]
-    SH_T(4);
     float mx0 = fmaxf(sacc[0][0], sacc[0][1]), mx1 = fmaxf(sacc[1][0], sacc[1][1]);      // two independent max3 chains
 #pragma unroll
     for (int i = 2; i < 16; i += 2) { mx0 = fmaxf(fmaxf(mx0, sacc[0][i]), sacc[0][i + 1]); mx1 = fmaxf(fmaxf(mx1, sacc[1][i]), sacc[1][i + 1]); }
@@ -289,7 +251,6 @@ __device__ __forceinline__ void sh_attend(ShSlot& s, bool fresh, const bf16* Kst
             for (int j = 0; j < 4; ++j) s.lsum = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, (unsigned)w[j]), ones, s.lsum, false);
         }
     }
-    SH_T(5);
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
@@ -305,8 +266,6 @@ __device__ __forceinline__ void sh_attend(ShSlot& s, bool fresh, const bf16* Kst
         }
         if (kb == 0) __builtin_amdgcn_sched_barrier(0);           // at most 8 transposed fragments in flight (VGPR budget: 128)
     }
-    if (ST) asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
-    SH_T(6);
 }
 
 // Normalise and store a slot's 32 x 64 output tile.  A lane pair (r, r + 32) holds one query row: lane half hh owns the
@@ -341,30 +300,27 @@ __device__ __forceinline__ void sh_zero_rows(const MhaDesc& p, long row0, int n,
     }
 }
 
-// MODE (diagnostic builds, never the product path): 1 = stream only (no scores), 2 = compute only (no K/V DMA: stale tiles),
-// 3 = stamped (g_sh_stamps)
-//
 // 16 waves, four per SIMD, ONE query slot per wave: waves 0-7 hold the "global" queries of the pass (the fusion chunk, or a
 // fully masked segment's chunk attending uniformly), waves 8-15 the "local" queries of the segment whose key tiles are being
 // swept.  Each SIMD then runs two global and two local waves; with four resident waves the LDS / MFMA latencies of one wave
 // are covered by the others without hand-interleaving (the first version of this kernel -- 8 waves with both slots in every
 // wave, 212 VGPRs, two waves per SIMD running the same code in lock-step -- measured 230-240 us at the bench shape with
 // 41 % of wave cycles parked and 22 % issue-stalled: no faster than the tile-per-block kernel).
-// VAR 1: two key tiles per workgroup barrier -- the loop body runs twice behind one s_barrier: half the barriers, half the points
-// at which 16 waves wait for the slowest one (a slot switch, a finish, a loader still issuing); the ring then holds the pair
-// being consumed and the pair in flight (4 stages, tiles issued one pair-iteration ahead of their use).
+// Only VAR 0 is built.  VAR 2, and the stamp arguments (ST, tt, tl) of sh_attend that no build fills any more, are still here for
+// one reason: without either of them hipcc emits three scalar instructions of the VAR 0 kernel differently (one s_mov of the loop
+// set-up moves, one branch tests the inverted mask), and the product kernel's instruction stream is what its measured speed rests
+// on.  They go with the next change that alters this kernel's code anyway.
 // VAR 2: the 16 ring pieces of a tile are issued by FOUR loader waves (12-15: K pieces 0-3 / 4-7, V pieces 0-3 / 4-7), every step,
 // instead of one rotating wave issuing all 16 every fourth step: an LDS-DMA instruction costs its issuer ~230 cycles, so the lone
 // loader needs ~3.7 k cycles for a tile -- most of a step -- and when it also holds queries (rows 128-255 of a segment: every
 // ragged split) its step runs long and the whole workgroup waits for it at the next barrier.
-template <int MODE, int VAR>
+template <int VAR>
 __global__ __launch_bounds__(1024) void mha_sh_fwd_kernel(MhaDesc p, int hpb) {
     __shared__ __attribute__((aligned(1024))) bf16 ringK[SH_NS][4096];
     __shared__ __attribute__((aligned(1024))) bf16 ringV[SH_NS][4096];
     __shared__ __attribute__((aligned(1024))) bf16 qst[16][32 * 64];       // wave-private Q staging: 32 rows x 64
     const int tid = threadIdx.x, lane = tid & 63, wave = sh_uni(tid >> 6), r = lane & 31, hh = lane >> 5;
-    const bool local = MODE == 4 ? false : wave >= 8;               // role of this wave (MODE 4, diagnostic: sixteen global waves --
-                                                                    // waves 8-15 repeat the fusion queries of 0-7: what would twice the global work per step cost?)
+    const bool local = wave >= 8;                                   // role of this wave
     const int qw = wave & 7;                                        // its 32-query block inside a 256-query chunk
     const int hgroups = p.H / hpb;
     const int b = blockIdx.x / hgroups, h0 = (blockIdx.x % hgroups) * hpb;
@@ -434,7 +390,7 @@ __global__ __launch_bounds__(1024) void mha_sh_fwd_kernel(MhaDesc p, int hpb) {
     int q0 = 0, q1 = 0, q2 = 0, nfl = 0;                            // VAR 2: sequence numbers of my pieces of the (up to three) tiles in flight
     auto issue_ring = [&]() {                                       // every wave advances the position; the step's loader issues
         if (VAR == 2) {
-            if (MODE != 2 && wave >= 12) {
+            if (wave >= 12) {
                 const long row0 = t_row(lt); const int n = t_info(lt) & 255;
                 const bool isv = wave >= 14;
                 const bf16* b_ = (isv ? vg + row0 * p.v_stride : kg + row0 * p.k_stride) + (h0 + lh) * 64;
@@ -445,7 +401,7 @@ __global__ __launch_bounds__(1024) void mha_sh_fwd_kernel(MhaDesc p, int hpb) {
                 vm += 4;
             }
             q0 = q1; q1 = q2; q2 = vm; ++nfl;
-        } else if (MODE != 2 && wave == 12 + (lj & 3)) {
+        } else if (wave == 12 + (lj & 3)) {
             const long row0 = t_row(lt); const int n = t_info(lt) & 255;
             const bf16* kb_ = kg + row0 * p.k_stride + (h0 + lh) * 64;
             const bf16* vb_ = vg + row0 * p.v_stride + (h0 + lh) * 64;
@@ -517,68 +473,41 @@ __global__ __launch_bounds__(1024) void mha_sh_fwd_kernel(MhaDesc p, int hpb) {
     find_next(0, 0, 0);
     if (nh >= 0) issue_q(nsg, chunk_of(np_), h0 + nh);
     mark = vm;
-    for (int i = 0; i < (VAR == 1 ? SH_NS : SH_D) && i < G; ++i) issue_ring();
+    for (int i = 0; i < SH_D && i < G; ++i) issue_ring();
 
     bool act = false, fresh = false;
     int t = 0, pi = 0, hi = 0;
-    constexpr bool ST = MODE == 3;
-    unsigned long long tt[16], tl = 0, t_loop = 0;
+    constexpr bool ST = false;
+    unsigned long long tt[16], tl = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) tt[i] = 0;
-    if (ST) { tl = sh_now(); t_loop = tl; }
     int stage = 0;                                                  // ring stage of tile g
     for (int g = 0; g < G; ++g) {
-        if (VAR != 1 || (g & 1) == 0) {
-            if (VAR == 2) { if (wave >= 12) sh_wait_vm(vm - (nfl >= 3 ? q0 : nfl == 2 ? q1 : q2)); --nfl; }     // my four pieces of tile g: the oldest in flight
-            else if (wave == 12 + (g & 3)) sh_wait_vm(vm - myseq);     // the pieces of tile g were mine to fetch
-            if (VAR == 1 && g + 1 < G && wave == 12 + ((g + 1) & 3)) sh_wait_vm(vm - myseq);
-            SH_T(0);
-            __builtin_amdgcn_s_barrier();
-            SH_T(1);
-            if (VAR != 1) { if (lj < G) issue_ring(); }
-            else if (g >= 2) { if (lj < G) issue_ring(); if (lj < G) issue_ring(); }   // into the stages of the pair just finished
-            if (VAR == 1 && SH_SKEW > 0 && wave >= 4 && wave < 8) __builtin_amdgcn_s_sleep(SH_SKEW);   // experiment: phase offset
-                                                                    // between the two global waves of a SIMD (units of 64 cycles)
-            if (SH_SLEEP_CLASS >= 0 && (wave >> 2) == SH_SLEEP_CLASS) __builtin_amdgcn_s_sleep(8);   // slack probe: 512 idle cycles per
-                                                                    // step in ONE wave class (0: waves 0-3 ... 3: 12-15, the loaders)
-        }
+        if (VAR == 2) { if (wave >= 12) sh_wait_vm(vm - (nfl >= 3 ? q0 : nfl == 2 ? q1 : q2)); --nfl; }     // my four pieces of tile g: the oldest in flight
+        else if (wave == 12 + (g & 3)) sh_wait_vm(vm - myseq);      // the pieces of tile g were mine to fetch
+        __builtin_amdgcn_s_barrier();
+        if (lj < G) issue_ring();
         const int tinf = t_info(t), kn = tinf & 255, sg = (tinf >> 8) & 255, fl = tinf >> 16;
         const int h = h0 + hi;
-        SH_T(2);
         // slot switch: a global wave at the first tile of its pass, a local wave at the first tile of its segment
         if (nh == hi && np_ == pi && (local ? ((fl & 1) && nsg == sg) : t == 0)) {
-            unsigned long long tl2 = tl;
             sh_wait_vm(vm - mark);
-            if (ST) { __builtin_amdgcn_sched_barrier(0); const unsigned long long n_ = sh_now(); tt[12] += n_ - tl2; tl2 = n_; __builtin_amdgcn_sched_barrier(0); }
             activate(nsg, chunk_of(pi), !local && nsg != fus);
             act = true; fresh = true;
             __builtin_amdgcn_sched_barrier(0);
-            if (ST) { const unsigned long long n_ = sh_now(); tt[13] += n_ - tl2; tl2 = n_; __builtin_amdgcn_sched_barrier(0); }
             if (local) find_next(hi, pi, sg + 1); else find_next(hi, pi + 1, 0);
-            if (ST) { __builtin_amdgcn_sched_barrier(0); const unsigned long long n_ = sh_now(); tt[14] += n_ - tl2; tl2 = n_; __builtin_amdgcn_sched_barrier(0); }
             if (nh >= 0) { issue_q(nsg, chunk_of(np_), h0 + nh); mark = vm; }
         }
-        SH_T(3);
         if (act) {
             unsigned kext[2];
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) kext[kb] = hh == 0 ? sh_pack2(1.0f, (32 * kb + r >= kn) ? -1.0e30f : 0.f) : 0u;
-            if (MODE != 1) sh_attend<ST>(S, fresh, ringK[0], ringV[0], stage * 4096, ad, kext, hh, tt, tl);
+            sh_attend<ST>(S, fresh, ringK[0], ringV[0], stage * 4096, ad, kext, hh, tt, tl);
             fresh = false;
-            if (ST) tt[9] += 1;
             if (local ? (fl & 2) != 0 : t == ntile - 1) { sh_finish(S, p, h, r, hh); act = false; vm += 5; }   // 4 row stores + lse
-            SH_T(7);
         }
         if (++stage == SH_NS) stage = 0;
         if (++t == ntile) { t = 0; if (++pi == npass) { pi = 0; ++hi; } }
-    }
-    if (ST) {
-        const unsigned w = blockIdx.x * 16 + wave;
-        if (lane == 0 && w < SH_STAMP_WAVES) {
-            tt[8] = sh_now() - t_loop; tt[10] = (unsigned long long)G; tt[11] = 1;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) g_sh_stamps[w][i] = tt[i];
-        }
     }
 }
 
@@ -599,7 +528,6 @@ __global__ __launch_bounds__(1024) void mha_sh_fwd_kernel(MhaDesc p, int hpb) {
 #define SD_MAXB 64              // key blocks per sample (one lane each)
 #define SD_MAXS 64              // ring steps per head (one lane each)
 
-template <int MODE>
 __global__ __launch_bounds__(SD_W * 64) void mha_sh_dkdv_kernel(MhaDesc p, int hpb) {
     __shared__ __attribute__((aligned(1024))) bf16 ringQ[SD_NS][4096];
     __shared__ __attribute__((aligned(1024))) bf16 ringO[SD_NS][4096];
@@ -672,7 +600,7 @@ __global__ __launch_bounds__(SD_W * 64) void mha_sh_dkdv_kernel(MhaDesc p, int h
     // ring: loader of step j is wave 8 + (j & 3) -- the waves that idle while the fusion keys' pass runs on eight waves
     int lj = 0, li = 0, lh = 0, lstage = 0;
     auto issue_ring = [&]() {
-        if (MODE != 2 && wave == 8 + (lj & 3)) {
+        if (wave == 8 + (lj & 3)) {
             const long row0 = s_row(li); const int n = s_info(li) & 255, h = h0 + lh;
             const bf16* qb_ = qg + row0 * p.q_stride + h * 64;
             const bf16* ob_ = dog + row0 * p.do_stride + h * 64;
@@ -761,7 +689,7 @@ __global__ __launch_bounds__(SD_W * 64) void mha_sh_dkdv_kernel(MhaDesc p, int h
             if (nxt_valid) { issue_kv(nxt_ps, h0 + nxt_h); mark = vm; }
         }
         const bool part = have && (mode == 2 || (mode == 1 && (sq == fus || sq == my_seg)));
-        if (part && MODE != 1) {
+        if (part) {
             const bf16* Qs = ringQ[0]; const bf16* Os = ringO[0];
             const int sel = stage * 4096;
             const int rbase = ad.krow0 + sel, tbase = ad.tr00 + sel;
@@ -880,7 +808,6 @@ __device__ __forceinline__ unsigned sq_split(float x) {
     return sh_pack2(hi, x - hi);
 }
 
-template <int MODE>
 __global__ __launch_bounds__(SQ_W * 64) void mha_sh_dq_kernel(MhaDesc p, int hpb) {
     __shared__ __attribute__((aligned(1024))) bf16 ringK[SQ_NS][4096];
     __shared__ __attribute__((aligned(1024))) bf16 ringV[SQ_NS][4096];
@@ -952,7 +879,7 @@ __global__ __launch_bounds__(SQ_W * 64) void mha_sh_dq_kernel(MhaDesc p, int hpb
     int lt = 0, lp = 0, lh = 0, lj = 0, lstage = 0;
     lt = seek(0, 0);
     auto issue_ring = [&]() {
-        if (MODE != 2 && wave == 8 + (lj & 3)) {
+        if (wave == 8 + (lj & 3)) {
             const long row0 = t_row(lt); const int n = t_info(lt) & 255, h = h0 + lh;
             int z = 0;
             asm volatile("" : "+s"(z));
@@ -1085,44 +1012,42 @@ __global__ __launch_bounds__(SQ_W * 64) void mha_sh_dq_kernel(MhaDesc p, int hpb
             do_stage2();
         }
         if (act) {
-            if (MODE != 1) {
-                const bf16* Kst = ringK[0]; const bf16* Vst = ringV[0];
-                const int sel = stage * 4096, kbase = ad.krow0 + sel, vbase = ad.tr00 + sel;
-                int zc = 0;                                        // (opaque zero: keeps the constant operand out of the loop-invariant set,
-                asm volatile("" : "+s"(zc));                       //  where it was spilled and reloaded from scratch every tile)
-                const bf16x8 kone = sh_ext((hh == 0 ? 0x3f803f80u : 0u) | (unsigned)zc), qeS = sh_ext(extS), qeD = sh_ext(extD);
-                f32x16 z16;
+            const bf16* Kst = ringK[0]; const bf16* Vst = ringV[0];
+            const int sel = stage * 4096, kbase = ad.krow0 + sel, vbase = ad.tr00 + sel;
+            int zc = 0;                                            // (opaque zero: keeps the constant operand out of the loop-invariant set,
+            asm volatile("" : "+s"(zc));                           //  where it was spilled and reloaded from scratch every tile)
+            const bf16x8 kone = sh_ext((hh == 0 ? 0x3f803f80u : 0u) | (unsigned)zc), qeS = sh_ext(extS), qeD = sh_ext(extD);
+            f32x16 z16;
 #pragma unroll
-                for (int i = 0; i < 16; ++i) z16[i] = 0.f;
+            for (int i = 0; i < 16; ++i) z16[i] = 0.f;
 #pragma unroll
-                for (int kb = 0; kb < 2; ++kb) {
-                    bf16x8 pb[2], dsb[2];
-                    {
-                        f32x16 sacc = sh_mma(kone, qeS, z16);
+            for (int kb = 0; kb < 2; ++kb) {
+                bf16x8 pb[2], dsb[2];
+                {
+                    f32x16 sacc = sh_mma(kone, qeS, z16);
 #pragma unroll
-                        for (int ks = 0; ks < 4; ++ks) sacc = sh_mma(sh_ld8(Kst + 2048 * kb + (kbase ^ (16 * ks))), q[ks], sacc);
+                    for (int ks = 0; ks < 4; ++ks) sacc = sh_mma(sh_ld8(Kst + 2048 * kb + (kbase ^ (16 * ks))), q[ks], sacc);
 #pragma unroll
-                        for (int s2 = 0; s2 < 2; ++s2)
+                    for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-                            for (int j = 0; j < 8; ++j) pb[s2][j] = (bf16)sh_exp2(sacc[8 * s2 + j]);
-                    }
-                    {
-                        f32x16 dpacc = sh_mma(kone, qeD, z16);
-#pragma unroll
-                        for (int ks = 0; ks < 4; ++ks) dpacc = sh_mma(sh_ld8(Vst + 2048 * kb + (kbase ^ (16 * ks))), dO[ks], dpacc);
-#pragma unroll
-                        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) dsb[s2][j] = (bf16)((float)pb[s2][j] * dpacc[8 * s2 + j]);
-                    }
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) {
-                        const bf16* kb_ = Kst + 64 * (32 * kb + 16 * s2);
-#pragma unroll
-                        for (int d = 0; d < 2; ++d) dq[d] = sh_mma(sh_tr(kb_, vbase ^ (32 * d), vbase ^ (32 * d + 520)), dsb[s2], dq[d]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
+                        for (int j = 0; j < 8; ++j) pb[s2][j] = (bf16)sh_exp2(sacc[8 * s2 + j]);
                 }
+                {
+                    f32x16 dpacc = sh_mma(kone, qeD, z16);
+#pragma unroll
+                    for (int ks = 0; ks < 4; ++ks) dpacc = sh_mma(sh_ld8(Vst + 2048 * kb + (kbase ^ (16 * ks))), dO[ks], dpacc);
+#pragma unroll
+                    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) dsb[s2][j] = (bf16)((float)pb[s2][j] * dpacc[8 * s2 + j]);
+                }
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const bf16* kb_ = Kst + 64 * (32 * kb + 16 * s2);
+#pragma unroll
+                    for (int d = 0; d < 2; ++d) dq[d] = sh_mma(sh_tr(kb_, vbase ^ (32 * d), vbase ^ (32 * d + 520)), dsb[s2], dq[d]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
             // last tile of the slot: a local wave's segment ends, a global wave's pass ends
             const int tn = seek(t + 1, pi);
@@ -1203,13 +1128,11 @@ __global__ __launch_bounds__(256) void mha_rowconst_kernel(MhaDesc p) {
     }
 }
 
-// MODE (diagnostic builds, never the product path; wrong dQ): 1 = no dS exchange and no dQ phase (the dK / dV part alone on eight waves),
-// 2 = dQ phase without the workspace traffic of the partials
 // RC (variant 55, not the product): the row constants of a tile (-lse log2 e, -delta = -rowsum(dO o O)) are formed HERE, one step ahead,
 // by the four loader waves while waves 0..3 run the dQ products, and written into the ring stage of the next step, instead of being read
 // from the planes of the pre-pass mha_rowconst_kernel.  Saves the pre-pass (62 us) and costs the kernel 35 (255 VGPRs instead of 232, the
 // loader waves reach the barrier later): -25 us per call in isolation, nothing measurable in the step.
-template <int MODE, bool RC = false>
+template <bool RC>
 __global__ __launch_bounds__(SB_W * 64) void mha_sh_bwd_kernel(MhaDesc p, int hpb) {
     __shared__ __attribute__((aligned(1024))) bf16 ringQ[SB_NS][4096];
     __shared__ __attribute__((aligned(1024))) bf16 ringO[SB_NS][4096];
@@ -1483,11 +1406,11 @@ __global__ __launch_bounds__(SB_W * 64) void mha_sh_bwd_kernel(MhaDesc p, int hp
             nxt_buf = cur_buf ^ 1;
             if (nxt_valid) { issue_kv(nxt_ps, h0 + nxt_h, nxt_buf); mark = vm; }
         }
-        const bool dq_wave = wave < 4 && mode == 1 && MODE != 1 && MODE != 4;      // MODE 4: dS exchange and barrier, no dQ products
+        const bool dq_wave = wave < 4 && mode == 1;
         // dQ^T quarter of waves 0..3: starts from the tile's partial of the earlier passes (prefetched here, used after the barrier)
         f32x16 dqa;
         float* wsq = p.dq_ws + ((((long)b * p.max_qt + s_tid(si)) * p.H + h) * 4 + (2 * dq_d + dq_q)) * 1024 + 4 * lane;
-        if (dq_wave && !tfirst && MODE == 0) {
+        if (dq_wave && !tfirst) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const f32x4 v4 = *reinterpret_cast<const f32x4*>(wsq + 256 * i);
@@ -1499,7 +1422,7 @@ __global__ __launch_bounds__(SB_W * 64) void mha_sh_bwd_kernel(MhaDesc p, int hp
             for (int i = 0; i < 16; ++i) dqa[i] = 0.f;
         }
         const bool part = have && (mode == 2 || (mode == 1 && (sq == fus || sq == my_seg)));
-        if (MODE != 1 && mode == 1 && have && !part) {
+        if (mode == 1 && have && !part) {
             // a key block that does not take part in this tile contributes dS = 0: the dQ phase then runs ONE branch-free chain over
             // every block of the pass (its K rows are finite: staged keys, zero rows beyond a block's end)
 #pragma unroll
@@ -1545,12 +1468,10 @@ __global__ __launch_bounds__(SB_W * 64) void mha_sh_bwd_kernel(MhaDesc p, int hp
                         for (int j = 0; j < 8; ++j) dsb[s2][j] = (bf16)((float)pb[s2][j] * dpacc[8 * s2 + j]);
                         // dS for the dQ phase: element j of this lane is query 32 qb + 16 s2 + 8 (j >> 2) + 4 hh + (j & 3) of key (wave, r):
                         // two 8-byte pieces of row 32 wave + r of the [key][q] image
-                        if (MODE != 1) {
-                            const u32x4 w4 = __builtin_bit_cast(u32x4, dsb[s2]);
-                            const int c0 = 4 * qb + 2 * s2;
-                            *reinterpret_cast<u32x2*>(dsx + dsw + 8 * (c0 ^ dsf) + 4 * hh) = u32x2{w4[0], w4[1]};
-                            *reinterpret_cast<u32x2*>(dsx + dsw + 8 * ((c0 + 1) ^ dsf) + 4 * hh) = u32x2{w4[2], w4[3]};
-                        }
+                        const u32x4 w4 = __builtin_bit_cast(u32x4, dsb[s2]);
+                        const int c0 = 4 * qb + 2 * s2;
+                        *reinterpret_cast<u32x2*>(dsx + dsw + 8 * (c0 ^ dsf) + 4 * hh) = u32x2{w4[0], w4[1]};
+                        *reinterpret_cast<u32x2*>(dsx + dsw + 8 * ((c0 + 1) ^ dsf) + 4 * hh) = u32x2{w4[2], w4[3]};
                     }
                 } else {
 #pragma unroll
@@ -1590,10 +1511,8 @@ __global__ __launch_bounds__(SB_W * 64) void mha_sh_bwd_kernel(MhaDesc p, int hp
             vm += 8;
         }
         // ---- dQ phase: every wave's dS block is in dsx, the pass's K images have been resident since its first step
-        if (MODE != 1) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
         if (rc_wave && g + 1 < G) {
             rc_finish(stage + 1 == SB_NS ? 0 : stage + 1);         // the next step's stage: its readers finished two barriers ago
             if (g + 2 < G) rc_issue_next();                         // a whole step in flight
@@ -1617,9 +1536,7 @@ __global__ __launch_bounds__(SB_W * 64) void mha_sh_bwd_kernel(MhaDesc p, int hp
                         dqa = sh_mma(sh_tr(Kc + ro, ka, kb2), sh_tr(dsx + ro, sa, sb2), dqa);
                     }
             }
-            if (!tlast && MODE == 2) {
-                asm volatile("" :: "v"(dqa));                      // keep the products live
-            } else if (!tlast) {                                   // carry the partial to the tile's next pass
+            if (!tlast) {                                          // carry the partial to the tile's next pass
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     *reinterpret_cast<f32x4*>(wsq + 256 * i) = f32x4{dqa[4 * i], dqa[4 * i + 1], dqa[4 * i + 2], dqa[4 * i + 3]};
@@ -1666,24 +1583,11 @@ bool mha_sh_applicable(const MhaDesc& d) {
            d.max_q_rows / 256 + 2 * d.nseg <= SH_MAXP;
 }
 
-int mha_sh_fwd(const MhaDesc& d, int mode, hipStream_t st) {
+int mha_sh_fwd(const MhaDesc& d, hipStream_t st) {
     if (d.max_k_rows / 64 + d.nseg > SH_MAXT || d.k_stride != d.v_stride || d.nseg > MAXSEG) return MMAE_ERR_ARG;
     const int hpb = sh_heads_per_block(d.B, d.H, d.hpb_req);
     const dim3 grid(d.B * (d.H / hpb)), blk(1024);
-    if (mode == 1) MMAE_LAUNCH((mha_sh_fwd_kernel<1, 0>), grid, blk, 0, st, d, hpb);
-    else if (mode == 2) MMAE_LAUNCH((mha_sh_fwd_kernel<2, 0>), grid, blk, 0, st, d, hpb);
-#if MMAE_DIAG
-    else if (mode == 3) MMAE_LAUNCH((mha_sh_fwd_kernel<3, 0>), grid, blk, 0, st, d, hpb);
-#else
-    else if (mode == 3) return MMAE_ERR_ARG;
-#endif
-    else if (mode == 10) MMAE_LAUNCH((mha_sh_fwd_kernel<0, 1>), grid, blk, 0, st, d, hpb);     // two tiles per barrier
-    else if (mode == 11) MMAE_LAUNCH((mha_sh_fwd_kernel<1, 1>), grid, blk, 0, st, d, hpb);
-    else if (mode == 12) MMAE_LAUNCH((mha_sh_fwd_kernel<2, 1>), grid, blk, 0, st, d, hpb);
-    else if (mode == 4) MMAE_LAUNCH((mha_sh_fwd_kernel<4, 0>), grid, blk, 0, st, d, hpb);      // diagnostic: sixteen global waves
-    else if (mode == 20) MMAE_LAUNCH((mha_sh_fwd_kernel<0, 2>), grid, blk, 0, st, d, hpb);     // four loader waves
-    else if (mode == 21) MMAE_LAUNCH((mha_sh_fwd_kernel<1, 2>), grid, blk, 0, st, d, hpb);
-    else MMAE_LAUNCH((mha_sh_fwd_kernel<0, 0>), grid, blk, 0, st, d, hpb);
+    MMAE_LAUNCH(mha_sh_fwd_kernel<0>, grid, blk, 0, st, d, hpb);
     MMAE_CHECK_LAUNCH();
     return MMAE_OK;
 }
@@ -1695,13 +1599,11 @@ bool mha_sh_dkdv_supported(const MhaDesc& d) {
     return nb <= SD_MAXB && d.nseg <= MAXSEG && passes * (d.max_q_rows / 64 + d.nseg + 1) <= SD_MAXS;
 }
 
-int mha_sh_dkdv(const MhaDesc& d, int mode, hipStream_t st) {
+int mha_sh_dkdv(const MhaDesc& d, hipStream_t st) {
     if (!mha_sh_dkdv_supported(d)) return MMAE_ERR_ARG;
     const int hpb = sh_heads_per_block(d.B, d.H, d.hpb_req);
     const dim3 grid(d.B * (d.H / hpb)), blk(SD_W * 64);
-    if (mode == 1) MMAE_LAUNCH(mha_sh_dkdv_kernel<1>, grid, blk, 0, st, d, hpb);
-    else if (mode == 2) MMAE_LAUNCH(mha_sh_dkdv_kernel<2>, grid, blk, 0, st, d, hpb);
-    else MMAE_LAUNCH(mha_sh_dkdv_kernel<0>, grid, blk, 0, st, d, hpb);
+    MMAE_LAUNCH(mha_sh_dkdv_kernel, grid, blk, 0, st, d, hpb);
     MMAE_CHECK_LAUNCH();
     return MMAE_OK;
 }
@@ -1713,22 +1615,18 @@ bool mha_sh_fused_supported(const MhaDesc& d) {
            d.max_qt >= d.max_q_rows / 64 + d.nseg;
 }
 
-int mha_sh_bwd_fused(const MhaDesc& d, int mode, hipStream_t st) {
+int mha_sh_bwd_fused(const MhaDesc& d, bool rc, hipStream_t st) {
     if (!mha_sh_fused_supported(d)) return MMAE_ERR_ARG;
-    // mode 0: product (row constants from the pre-pass mha_rowconst_kernel); 1 / 2 / 4: its diagnostic builds; 3: without the pre-pass (stale
-    // planes, timing only); 5: row constants formed inside the kernel by the loader waves (RC; correct results: isolated -25 us per call at
-    // the bench shape, +-0 in the step -- DESIGN.md section 4)
-    if (mode != 3 && mode != 5) {
+    // rc false: product (row constants from the pre-pass mha_rowconst_kernel); true: row constants formed inside the kernel by the loader
+    // waves (RC; correct results: isolated -25 us per call at the bench shape, +-0 in the step -- DESIGN.md section 4)
+    if (!rc) {
         MMAE_LAUNCH(mha_rowconst_kernel, dim3((unsigned)((d.stat_stride + 31) / 32)), dim3(256), 0, st, d);
         MMAE_CHECK_LAUNCH();
     }
     const int hpb = sh_heads_per_block(d.B, d.H, d.hpb_req);
     const dim3 grid(d.B * (d.H / hpb)), blk(SB_W * 64);
-    if (mode == 1) MMAE_LAUNCH((mha_sh_bwd_kernel<1, false>), grid, blk, 0, st, d, hpb);
-    else if (mode == 2) MMAE_LAUNCH((mha_sh_bwd_kernel<2, false>), grid, blk, 0, st, d, hpb);
-    else if (mode == 4) MMAE_LAUNCH((mha_sh_bwd_kernel<4, false>), grid, blk, 0, st, d, hpb);
-    else if (mode == 5) MMAE_LAUNCH((mha_sh_bwd_kernel<0, true>), grid, blk, 0, st, d, hpb);
-    else MMAE_LAUNCH((mha_sh_bwd_kernel<0, false>), grid, blk, 0, st, d, hpb);
+    if (rc) MMAE_LAUNCH(mha_sh_bwd_kernel<true>, grid, blk, 0, st, d, hpb);
+    else MMAE_LAUNCH(mha_sh_bwd_kernel<false>, grid, blk, 0, st, d, hpb);
     MMAE_CHECK_LAUNCH();
     return MMAE_OK;
 }
@@ -1738,13 +1636,11 @@ bool mha_sh_dq_supported(const MhaDesc& d) {
     return d.max_k_rows / 64 + d.nseg <= SQ_MAXT && d.nseg <= MAXSEG && d.max_q_rows / 128 + 1 <= SQ_MAXP;
 }
 
-int mha_sh_dq(const MhaDesc& d, int mode, hipStream_t st) {
+int mha_sh_dq(const MhaDesc& d, hipStream_t st) {
     if (!mha_sh_dq_supported(d)) return MMAE_ERR_ARG;
     const int hpb = sh_heads_per_block(d.B, d.H, d.hpb_req);
     const dim3 grid(d.B * (d.H / hpb)), blk(SQ_W * 64);
-    if (mode == 1) MMAE_LAUNCH(mha_sh_dq_kernel<1>, grid, blk, 0, st, d, hpb);
-    else if (mode == 2) MMAE_LAUNCH(mha_sh_dq_kernel<2>, grid, blk, 0, st, d, hpb);
-    else MMAE_LAUNCH(mha_sh_dq_kernel<0>, grid, blk, 0, st, d, hpb);
+    MMAE_LAUNCH(mha_sh_dq_kernel, grid, blk, 0, st, d, hpb);
     MMAE_CHECK_LAUNCH();
     return MMAE_OK;
 }

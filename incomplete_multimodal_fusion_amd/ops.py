@@ -753,7 +753,7 @@ class _MHA(torch.autograd.Function):
         fused = (not variant and MHA_FUSED_BWD and qt.dtype == torch.bfloat16 and dh == 64 and qseg.max_rows >= 128 and kseg.max_rows >= 128 and
                  (kseg.max_rows // 32 + kseg.nseg + 7) // 8 <= MHA_FUSED_MAX_PASSES and
                  bool(lib_.mmae_mha_bwd_fused_supported(dt(qt), dh, qseg.B, H, qseg.nseg, qseg.max_rows, kseg.max_rows)))
-        if fused or (variant > 0 and 50 <= (variant & 255) <= 55):      # planes + fp32 partial dQ tiles
+        if fused or (variant > 0 and (variant & 255) in (50, 55)):      # planes + fp32 partial dQ tiles
             nws = lib_.mmae_mha_bwd_fused_ws_floats(qseg.B, H, qseg.nseg, lse.shape[1], qseg.max_rows)
         else:
             nws = lib_.mmae_mha_bwd_ws_floats(H, lse.shape[1])
@@ -800,8 +800,9 @@ MHA_FUSED_MAX_PASSES = 3   # ... and only while a sample's keys fit this many pa
 
 
 def _variant_word(variant: int, hpb: int) -> int:
-    """csrc/mmae_internal.h: bits 0..7 of a non-negative variant name the kernel, bits 8..11 the heads one workgroup of the
-    sample-head kernels walks (0: chosen from (B, H) as the product path does)."""
+    """csrc/mmae_internal.h: bits 0..7 of a non-negative variant name the kernel (0, 2, 4, 5, 23, 50 or 55; the library rejects
+    every other number), bits 8..11 the heads one workgroup of the sample-head kernels walks (0: chosen from (B, H) as the
+    product path does)."""
     assert 0 <= hpb < 16
     return variant if (variant < 0 or not hpb) else (variant | (hpb << 8))
 
@@ -809,7 +810,8 @@ def _variant_word(variant: int, hpb: int) -> int:
 def mha_self(qkv: torch.Tensor, H: int, dh: int, seg: Segments, scale: float, order: str = "qkv", variant: Optional[int] = None,
              hpb: int = 0) -> torch.Tensor:
     """Self attention on a fused projection output qkv (rows, 3*H*dh) laid out [q | k | v] column blocks.
-    variant != 0 / hpb != 0: test / tuning kernels through csrc/mmae_internal.h (per call, no global state)."""
+    variant != 0 / hpb != 0: test / tuning kernels through csrc/mmae_internal.h (per call, no global state); variant is -1 or one
+    of the numbers of that header's table -- any other raises MmaeLibraryError.  dh != 64 has no variants: it runs variant 0."""
     variant = MHA_SELF_VARIANT if variant is None else variant
     if variant and dh != 64:
         variant = 0
@@ -819,7 +821,7 @@ def mha_self(qkv: torch.Tensor, H: int, dh: int, seg: Segments, scale: float, or
 
 def mha_cross(q: torch.Tensor, kv: torch.Tensor, H: int, dh: int, qseg: Segments, kseg: Segments, scale: float,
               empty_mode: int = 0, variant: int = 0, hpb: int = 0) -> torch.Tensor:
-    """q (rows_q, H*dh), kv (rows_k, 2*H*dh) = [k | v]."""
+    """q (rows_q, H*dh), kv (rows_k, 2*H*dh) = [k | v].  variant / hpb as in mha_self (csrc/mmae_internal.h)."""
     return _MHA.apply(q, kv, 0, 0, H * dh, H, dh, qseg, kseg, scale, empty_mode, _variant_word(variant, hpb))
 
 

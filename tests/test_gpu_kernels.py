@@ -674,7 +674,7 @@ def test_mha_bf16_fast_path_matches_generic_kernels(dh):
     g = torch.randn(r, I, device=DEV).to(torch.bfloat16)
     res = []
     # -1: generic dtype-templated kernels (csrc/mmae_internal.h), 0: bf16 fast path (dh 64: 32x32x16 forward), 2: the round-1
-    # 16x16x32 forward, 4: 256-query tiles, 5: sample-head dQ (the stamped diagnostic builds 8 / 9 exist in `make DIAG=1` only)
+    # 16x16x32 forward, 4: 256-query tiles, 5: sample-head dQ, 50 / 55: fused backward (the table in csrc/mmae_internal.h)
     for variant in ((-1, 0, 2, 4, 5, 50, 55) if dh == 64 else (-1, 0)):
         x = qkv.clone().requires_grad_()
         out = ops.mha_self(x, H, dh, seg, dh ** -0.5, variant=variant)
@@ -682,6 +682,42 @@ def test_mha_bf16_fast_path_matches_generic_kernels(dh):
         res.append((out.float(), x.grad.float()))
     for i in range(1, len(res)):
         close(res[i][0], res[0][0], 1e-2, "out"); close(res[i][1], res[0][1], 2e-2, "grads")
+
+
+def test_mha_unknown_variant_is_rejected():
+    """The variant numbers of csrc/mmae_internal.h are -1, 0, 2, 4, 5, 23, 50 and 55.  Every other number -- the retired experiment
+    builds and anything never defined -- is an argument error of both *_variant entry points, raised before a kernel is launched,
+    with or without the heads-per-workgroup bits.  One 64-row segment: whatever a library without the check ran was a valid launch."""
+    import ctypes
+    from incomplete_multimodal_fusion_amd import _lib, ops
+    from incomplete_multimodal_fusion_amd._lib import MmaeLibraryError, dt, ptr, stream
+    torch.manual_seed(11)
+    B, H, dh, n = 1, 1, 64, 64
+    I = H * dh
+    seg = ops.Segments.dense(B, n, DEV)
+    qkv = torch.randn(n, 3 * I, device=DEV).to(torch.bfloat16)
+    for v in (1, 3, 6, 7, 8, 9, 18, 22, 30, 31, 32, 35, 40, 41, 45, 51, 52, 53, 54, 99):
+        with pytest.raises(MmaeLibraryError):
+            ops.mha_self(qkv, H, dh, seg, dh ** -0.5, variant=v)
+    with pytest.raises(MmaeLibraryError):
+        ops.mha_self(qkv, H, dh, seg, dh ** -0.5, variant=7, hpb=1)
+    # backward: the tensors of a valid variant-0 forward, then one direct call with a retired number
+    out = torch.empty(n, I, dtype=torch.bfloat16, device=DEV)
+    lse = torch.empty(H, n, dtype=torch.float32, device=DEV)
+    es = qkv.element_size()
+    col = lambda t, c: ctypes.c_void_p(t.data_ptr() + c * es)
+    _lib.call("mmae_mha_fwd_variant", dt(qkv), dh, B, H, seg.nseg, col(qkv, 0), col(qkv, I), col(qkv, 2 * I), ptr(out), ptr(lse),
+              qkv.stride(0), qkv.stride(0), qkv.stride(0), out.stride(0), n, ptr(seg.start), ptr(seg.length), ptr(seg.start),
+              ptr(seg.length), n, n, dh ** -0.5, 0, 0, stream())
+    gout = torch.randn(n, I, device=DEV).to(torch.bfloat16)
+    gqkv = torch.zeros_like(qkv)
+    ws = torch.empty(_lib.lib().mmae_mha_bwd_fused_ws_floats(B, H, seg.nseg, n, n), dtype=torch.float32, device=DEV)
+    with pytest.raises(MmaeLibraryError):
+        _lib.call("mmae_mha_bwd_variant", dt(qkv), dh, B, H, seg.nseg, col(qkv, 0), col(qkv, I), col(qkv, 2 * I), ptr(out), ptr(gout),
+                  ptr(lse), ptr(ws), col(gqkv, 0), col(gqkv, I), col(gqkv, 2 * I), qkv.stride(0), qkv.stride(0), qkv.stride(0),
+                  out.stride(0), gout.stride(0), gqkv.stride(0), gqkv.stride(0), gqkv.stride(0), n, ptr(seg.start), ptr(seg.length),
+                  ptr(seg.start), ptr(seg.length), n, n, dh ** -0.5, 0, 51, stream())
+    torch.cuda.synchronize()
 
 
 def test_colsum_bias_gradient_kernel():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Micro-benchmark of the masked attention kernels at the bench workload's shapes (one process, interleaved variants).
 
-    python tools/bench_attn.py [--B 256] [--variants 0,1,...]      variant = per-call kernel variant (csrc/mmae_internal.h)
+    python tools/bench_attn.py [--B 256] [--variants 0,2,...]     variant = per-call kernel variant (csrc/mmae_internal.h)
 """
 import argparse, sys, os, time
 import torch
@@ -13,7 +13,8 @@ ap.add_argument("--B", type=int, default=256)
 ap.add_argument("--H", type=int, default=8)
 ap.add_argument("--dh", type=int, default=64)
 ap.add_argument("--variants", default="0", help="0: product kernels (dh 64 forward = 32x32x16, backward = the fused dQ + dK + dV kernel), 2: round-1 "
-                "16x16x32 forward, 4: 256-query tiles, 5: sample-head dQ + dK/dV pair, 50: fused backward, 51-54: its diagnostics, 55: row constants formed in the kernel (no pre-pass)")
+                "16x16x32 forward, 4: 256-query tiles, 5: sample-head forward + dQ + dK/dV, 23: head-looping dQ, 50: fused backward, 55: row constants formed in the kernel (no pre-pass); "
+                "the library rejects every other number")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--split", default="128,128,128", help="kept tokens per modality (N = sum), P = 256 fusion tokens")
