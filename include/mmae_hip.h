@@ -28,7 +28,8 @@ extern "C" {
                                 from 4 to 8 floats (mmae_adamw_control / _step_ctl read [4], [5]); + mmae_adamw_tick, mmae_mha_fwd_route.  6: + mmae_pad_copy_bf16_batched
                                 (additive: no existing signature changed).  7: + mmae_mha_bwd_fused, mmae_mha_bwd_fused_supported, mmae_mha_bwd_fused_ws_floats
                                 (additive); later additive entry points keep 7: mmae_trunc_standardize, mmae_bilstm_cell1_fwd / _bwd,
-                                mmae_bilstm_cell2_pool_fwd / _bwd, mmae_argmax_confusion, mmae_label_confusion, mmae_confusion_scores */
+                                mmae_bilstm_cell2_pool_fwd / _bwd, mmae_argmax_confusion, mmae_label_confusion, mmae_confusion_scores,
+                                mmae_query_semseg, mmae_query_confusion, mmae_query_dice_ws_floats, mmae_query_dice */
 int mmae_abi_version(void);
 /* hipError_t of this thread's most recent launch that returned MMAE_ERR_LAUNCH (0: none); reading resets it. */
 int mmae_last_hip_error(void);
@@ -295,6 +296,39 @@ int mmae_label_confusion(long n, const long long* gt, const long long* pred, int
  *   out[3] number of existing classes, rows with row_i > 0 (metrics.py:19-20);
  *   out[4 .. 4+K) the per-class IoU terms of out[0]; out[4+K .. 4+2K) per-class recall cm[i,i] / row_i (get_sa), 0 where row_i == 0. */
 int mmae_confusion_scores(int K, const long long* conf, double* out, void* stream);
+
+/* ---- Mask2Former semantic inference (DS/maskformer_train_seg.py:258-265 with semantic_inference :304-308; the same lines in
+ * DS/mask2former_infer_seg.py:185-259 and downstream/instance_segmentation/maskformer_train_{seg,ins,ins_vit}.py,
+ * mask2former_infer{,2json}.py) ---------------------------------------------------------------------------------------------
+ *   mask_pred = F.interpolate(pred_masks, size=(H, W), mode="bilinear", align_corners=False)
+ *   semseg    = einsum("bqc,bqhw->bchw", softmax(pred_logits, -1) without column void_index, sigmoid(mask_pred))
+ * in one kernel: neither the upsampled masks nor their sigmoid exist in memory.  pred_logits (B,Q,K1), pred_masks (B,Q,h,w), each
+ * fp32 or bf16 on its own (widened exactly; all arithmetic fp32).  K1 counts every column; void_index in [-1, K1) names the column
+ * that is dropped AFTER the softmax (-1: none; the reference drops 0, stock Mask2Former K1 - 1), leaving K kept classes in
+ * their original order.  Bilinear taps as ATen's align_corners=False kernel, for any h, w, H, W >= 1 (up, identity, down; no
+ * antialiasing): scale = (float)h / H, src = max(fmaf(y + 0.5f, scale, -0.5f), 0) (ATen's (y + 0.5f) * scale - 0.5f with one
+ * rounding instead of two), y0 = min((int)src, h - 1), y1 = min(y0 + 1, h - 1),
+ * lambda = src - y0, the same along x; the interpolation runs on the mask logits, sigmoid 1 / (1 + expf(-m)) after it; queries are
+ * summed in ascending order with fma.  The three entry points share that routine and agree bit for bit.
+ * Limits (MMAE_ERR_ARG): 1 <= Q <= 256, 1 <= K <= 64, 1 <= Kc <= 128, B*H*W < 2^31, h*w < 2^31; pointers need element alignment only.
+ * mmae_query_semseg: scores (B,K,H,W) fp32 and / or labels (B,H,W) int64 = argmax_c + label_offset (one of the two may be NULL);
+ * argmax as mmae_argmax_confusion: lowest index among equal maxima, the first NaN wins. */
+int mmae_query_semseg(int logit_dtype, int mask_dtype, int B, int Q, int K1, int h, int w, int H, int W, const void* pred_logits,
+                      const void* pred_masks, int void_index, float* scores, long long* labels, int label_offset, void* stream);
+/* conf_mat.add_batch(target, semseg.max(1)[1] + 1) of DS/maskformer_train_seg.py:266-270 without the label map: per pixel
+ * p = argmax_c + pred_offset, g = target (B,H,W) int64, conf[g*Kc + p] += 1 under the dropping rules of mmae_argmax_confusion
+ * (g == ignore_label, negative: none; g or p outside [0, Kc)).  conf (Kc,Kc) int64 is ACCUMULATED into; exact. */
+int mmae_query_confusion(int logit_dtype, int mask_dtype, int B, int Q, int K1, int h, int w, int H, int W, const void* pred_logits,
+                         const void* pred_masks, int void_index, const long long* target, int Kc, int pred_offset,
+                         long ignore_label, long long* conf, void* stream);
+/* floats of mmae_query_dice's workspace: 3 * K1 per 16 x 16 output tile; MMAE_ERR_ARG for a non-positive or too large shape. */
+long mmae_query_dice_ws_floats(int B, int K1, int H, int W);
+/* the sums of _get_dice (DS/maskformer_train_seg.py:272-274, :287-302) for EVERY sample: sums (B,K,3) fp64 = sum over the pixels
+ * of p*t, p, t with p the score of class c and t = (target - label_offset == c).  fp32 partials per tile in ws, added in fp64 in a
+ * fixed order by a second kernel: no float atomics, bitwise reproducible. */
+int mmae_query_dice(int logit_dtype, int mask_dtype, int B, int Q, int K1, int h, int w, int H, int W, const void* pred_logits,
+                    const void* pred_masks, int void_index, const long long* target, int label_offset, float* ws, double* sums,
+                    void* stream);
 
 /* ---- two-step BiLSTM fusion + attention pooling (MM/multimae_lstm_s2dsm.py:428-434 with DSI-MM/zorro_utils.py:261-299) ----------
  * Every row j < R is the length-2 sequence (x0_j, x1_j) through nn.LSTM(D, D, bidirectional), h0 = c0 = 0, gates i, f, g, o;

@@ -14,6 +14,7 @@
 //   confusion_scores_kernel: one workgroup; integer row / column sums, one fp64 division per score.
 // A launch counts fewer than 2^31 pixels, so a 32-bit LDS bin cannot wrap.
 #include "common.hpp"
+#include "confhist.hpp"
 #include "mmae_hip.h"
 
 #define SM_THREADS 1024                              // 16 waves share one LDS histogram: few workgroups, few flushes
@@ -32,37 +33,6 @@ template <> __device__ __forceinline__ f32x4 sm_ld4<bf16>(const bf16* p) {
     return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
 }
 
-// Bin of one (gt, pred) pair, -1 when the pair is dropped: gt == ignore_label, or either label outside [0, K).
-__device__ __forceinline__ int sm_bin(long long g, long long p, int K, long long ignore_label) {
-    const bool ok = g != ignore_label && g >= 0 && g < (long long)K && p >= 0 && p < (long long)K;
-    return ok ? (int)g * K + (int)p : -1;
-}
-
-// One histogram increment per lane (bin < 0: none); wave-uniform control flow required.  Class maps are smooth: most of a wave
-// falls into the bin of its first active lane, and those lanes are added by ONE LDS atomic; the others add 1 each.
-__device__ __forceinline__ void sm_hist_add(unsigned* h, int bin, int lane) {
-    const unsigned long long act = __ballot(bin >= 0);
-    if (act == 0) return;
-    const int leader = __builtin_ctzll(act);
-    const int b0 = __builtin_amdgcn_readlane(bin, leader);
-    const unsigned long long same = __ballot(bin == b0);
-    if (lane == leader) atomicAdd(h + b0, (unsigned)__popcll(same));
-    else if (bin >= 0 && bin != b0) atomicAdd(h + bin, 1u);
-}
-
-__device__ __forceinline__ void sm_hist_clear(unsigned* h, int K) {
-    for (int i = threadIdx.x; i < K * K; i += SM_THREADS) h[i] = 0u;
-    __syncthreads();
-}
-
-__device__ __forceinline__ void sm_hist_flush(const unsigned* h, int K, long long* conf) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < K * K; i += SM_THREADS) {
-        const unsigned v = h[i];
-        if (v) atomicAdd(reinterpret_cast<unsigned long long*>(conf) + i, (unsigned long long)v);
-    }
-}
-
 struct ArgmaxDesc {
     const void* pred; const long long* tgt; const long long* mask; long long* conf;
     long rows; int P, C, H, W, ps, K, pred_offset; long long ignore_label;
@@ -73,7 +43,7 @@ struct ArgmaxDesc {
 template <typename T, bool TOKENS>
 __global__ __launch_bounds__(SM_THREADS) void argmax_confusion_kernel(ArgmaxDesc d) {
     extern __shared__ unsigned sm_hist[];
-    sm_hist_clear(sm_hist, d.K);
+    sm_hist_clear<SM_THREADS>(sm_hist, d.K);
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int ps2 = d.ps * d.ps, nw = d.W / d.ps;
     const long HW = (long)d.H * d.W;
@@ -113,20 +83,20 @@ __global__ __launch_bounds__(SM_THREADS) void argmax_confusion_kernel(ArgmaxDesc
                 sm_hist_add(sm_hist, on ? sm_bin(g[j], (long long)idx[j] + d.pred_offset, d.K, d.ignore_label) : -1, lane);
         }
     }
-    sm_hist_flush(sm_hist, d.K, d.conf);
+    sm_hist_flush<SM_THREADS>(sm_hist, d.K, d.conf);
 }
 
 __global__ __launch_bounds__(SM_THREADS) void label_confusion_kernel(long n, const long long* __restrict__ gt,
                                                                      const long long* __restrict__ pred, int K,
                                                                      long long ignore_label, long long* conf) {
     extern __shared__ unsigned sm_hist[];
-    sm_hist_clear(sm_hist, K);
+    sm_hist_clear<SM_THREADS>(sm_hist, K);
     const int lane = threadIdx.x & (WAVE - 1);
     for (long base = (long)blockIdx.x * SM_THREADS; base < n; base += (long)gridDim.x * SM_THREADS) {   // block-uniform
         const long i = base + threadIdx.x;
         sm_hist_add(sm_hist, i < n ? sm_bin(gt[i], pred[i], K, ignore_label) : -1, lane);
     }
-    sm_hist_flush(sm_hist, K, conf);
+    sm_hist_flush<SM_THREADS>(sm_hist, K, conf);
 }
 
 // out[0] mIoU, [1] AA, [2] overall accuracy, [3] existing classes, [4, 4+K) per-class IoU, [4+K, 4+2K) per-class recall.

@@ -11,6 +11,11 @@ Beyond the reference:
     image or on the decoder's token-major output (multimae_crossattn.PredTokens), optionally over the masked patches only;
   scores(): the device tensor of ops.confusion_scores (mIoU, AA, overall accuracy, existing classes, per-class IoU and recall).
 
+The Mask2Former tail of the same evaluation loop (maskformer_train_seg.py:258-308), on the kernel of csrc/query_semseg.hip:
+  semantic_inference(mask_cls, mask_pred, size=None): the reference's method, with the bilinear resize folded in;
+  ConfMatrix.add_queries(pred_logits, pred_masks, gt): the body of evaluate(mode='eval') in one launch;
+  dice(pred_logits, pred_masks, target): the other mode's _get_dice, for every sample of the batch.
+
 Deliberate deviations:
   * `state` is a (K, K) int64 tensor on the device; the reference keeps float64 numpy.  Counts are exact either way;
   * the leftover `assert gt.shape == (64, 64)` of metrics.py:26 is not mirrored: any shape counts;
@@ -74,6 +79,14 @@ class ConfMatrix:
                              ignore_label=ignore_label)
         return None
 
+    def add_queries(self, pred_logits, pred_masks, gt, void_index: int = 0, pred_offset: int = 1, ignore_label: int = 0):
+        """evaluate(mode='eval') of maskformer_train_seg.py:258-270 in one launch: the masks (B, Q, h, w) resized bilinearly to
+        gt's (H, W), sigmoid, mixed by softmax(pred_logits (B, Q, K1)) without column void_index, and
+        state[gt, argmax + pred_offset] += 1.  The defaults are the reference's: class 0 dropped, + 1, gt == 0 ignored."""
+        ops.query_confusion(_on(pred_logits, self.device), _on(pred_masks, self.device), _on(gt, self.device), self.num_classes,
+                            conf=self.state, void_index=void_index, pred_offset=pred_offset, ignore_label=ignore_label)
+        return None
+
     def scores(self) -> torch.Tensor:
         """(4 + 2K,) float64 on the device, see ops.confusion_scores.  No host synchronisation."""
         return ops.confusion_scores(self.state)
@@ -123,6 +136,27 @@ def _infer_patch(shape, mask):
         if H % p == 0 and W % p == 0:
             return p
     raise ValueError("add_logits: H and W must be multiples of 4 (got %d x %d)" % (H, W))
+
+
+def semantic_inference(mask_cls, mask_pred, size=None):
+    """semantic_inference of maskformer_train_seg.py:304-308: softmax(mask_cls, -1)[..., 1:] mixed with mask_pred.sigmoid() by
+    einsum("bqc,bqhw->bchw") (batched: (B, Q, K1) and (B, Q, h, w)) or "qc,qhw->chw" (per image: (Q, K1) and (Q, h, w), the form of
+    mask2former_infer_seg.py).  The reference resizes the masks before the call; here `size` = (H, W) folds that
+    F.interpolate(..., mode="bilinear", align_corners=False) in, None keeps the masks' size.  fp32 scores on the device."""
+    if mask_cls.dim() == 2:
+        return ops.query_semseg(mask_cls[None], mask_pred[None], size=size, void_index=0)[0]
+    return ops.query_semseg(mask_cls, mask_pred, size=size, void_index=0)
+
+
+def dice(pred_logits, pred_masks, target, smooth: float = 1e-5):
+    """_get_dice of maskformer_train_seg.py:287-295 on semantic_inference's scores and the one-hot target without class 0
+    (:297-302), masks resized to target's (H, W): element b is sum_c(2 * num_c + smooth) / sum_c(den_c + smooth) of sample b, with
+    num_c = sum(p_c * t_c) and den_c = sum(p_c) + sum(t_c) over the pixels.  Returns a (B,) float64 device tensor without a host
+    synchronisation.  The reference only ever evaluates sample 0 of a batch (`pred_masks[0]`, `target[0]`, :272-274): that is
+    dice(...)[0]."""
+    s = ops.query_dice_sums(pred_logits, pred_masks, target, void_index=0, label_offset=1)
+    num, den = s[..., 0], s[..., 1] + s[..., 2]
+    return (2 * num + smooth).sum(-1) / (den + smooth).sum(-1)
 
 
 def AA(gt, pred, num_classes, device=None):

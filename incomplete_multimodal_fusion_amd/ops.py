@@ -1642,6 +1642,96 @@ def confusion_scores(conf: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------------------------ Mask2Former semantic inference
+def _query_args(name, pred_logits, pred_masks, size, void_index):
+    """Checks the two head outputs and returns (logits, masks, (B, Q, K1, h, w, H, W), K), contiguous, fp32 or bf16 each."""
+    if pred_logits.dim() != 3 or pred_masks.dim() != 4 or tuple(pred_masks.shape[:2]) != tuple(pred_logits.shape[:2]):
+        raise ValueError("%s: pred_logits (B, Q, K1) and pred_masks (B, Q, h, w) expected (got %s and %s)" %
+                         (name, tuple(pred_logits.shape), tuple(pred_masks.shape)))
+    ptr(pred_logits); ptr(pred_masks)                                       # host tensors: refused before anything is allocated
+    dt(pred_logits); dt(pred_masks)
+    B, Q, K1 = pred_logits.shape
+    h, w = pred_masks.shape[2:]
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    void_index = int(void_index)
+    if not -1 <= void_index < K1:
+        raise ValueError("%s: void_index %d outside [-1, %d)" % (name, void_index, K1))
+    return _c(pred_logits.detach()), _c(pred_masks.detach()), (B, Q, K1, h, w, H, W), K1 - (void_index >= 0)
+
+
+def _query_target(name, target, B):
+    if target.dim() != 3 or target.shape[0] != B:
+        raise ValueError("%s: a (B, H, W) target with B = %d expected (got %s)" % (name, B, tuple(target.shape)))
+    ptr(target)
+    return _c(target.detach().to(torch.int64))
+
+
+def query_semseg(pred_logits, pred_masks, size=None, void_index: int = 0):
+    """Mask2Former semantic inference (maskformer_train_seg.py:258-265, 304-308) in one kernel:
+    einsum("bqc,bqhw->bchw", softmax(pred_logits, -1) without column void_index, sigmoid(bilinear(pred_masks, size))).
+    pred_logits (B,Q,K1), pred_masks (B,Q,h,w), fp32 or bf16 each; size (H, W), None: the masks' own size; void_index -1 drops
+    no column (the reference drops 0, stock Mask2Former K1 - 1).  Returns the (B,K,H,W) fp32 scores.  Not differentiable."""
+    with torch.no_grad():
+        lg, mk, dims, K = _query_args("query_semseg", pred_logits, pred_masks, size, void_index)
+        B, H, W = dims[0], dims[5], dims[6]
+        scores = torch.empty(B, K, H, W, dtype=torch.float32, device=lg.device)
+        if scores.numel():
+            call("mmae_query_semseg", dt(lg), dt(mk), *dims, ptr(lg), ptr(mk), int(void_index), ptr(scores), None, 0, stream())
+    return scores
+
+
+def query_labels(pred_logits, pred_masks, size=None, void_index: int = 0, label_offset: int = 1):
+    """argmax over the classes of query_semseg's scores + label_offset (`semseg.max(1)[1] + 1`, maskformer_train_seg.py:270) as a
+    (B,H,W) int64 map, the scores never written.  torch.argmax's rule: lowest index among equal maxima, the first NaN wins."""
+    with torch.no_grad():
+        lg, mk, dims, _ = _query_args("query_labels", pred_logits, pred_masks, size, void_index)
+        B, H, W = dims[0], dims[5], dims[6]
+        labels = torch.empty(B, H, W, dtype=torch.int64, device=lg.device)
+        if labels.numel():
+            call("mmae_query_semseg", dt(lg), dt(mk), *dims, ptr(lg), ptr(mk), int(void_index), None, ptr(labels),
+                 int(label_offset), stream())
+    return labels
+
+
+def query_confusion(pred_logits, pred_masks, target, K: int, conf: Optional[torch.Tensor] = None, void_index: int = 0,
+                    pred_offset: int = 1, ignore_label: int = 0):
+    """The evaluate(mode='eval') body of maskformer_train_seg.py:258-270 in one kernel: the (gt, query_labels) pairs counted into
+    the (K,K) int64 matrix, masks resized to target's (H, W); neither scores nor labels are written.  The dropping rules of
+    argmax_confusion: target == ignore_label (negative: none), target or prediction outside [0, K).  Returns the matrix,
+    accumulated in place when `conf` is given.  Not differentiable; no host sync."""
+    with torch.no_grad():
+        if target.dim() != 3:
+            raise ValueError("query_confusion: a (B, H, W) target expected (got %s)" % (tuple(target.shape),))
+        lg, mk, dims, _ = _query_args("query_confusion", pred_logits, pred_masks, target.shape[1:], void_index)
+        target = _query_target("query_confusion", target, dims[0])
+        conf = _conf_buffer(conf, K, lg.device)
+        if target.numel():
+            call("mmae_query_confusion", dt(lg), dt(mk), *dims, ptr(lg), ptr(mk), int(void_index), ptr(target), K,
+                 int(pred_offset), int(ignore_label), ptr(conf), stream())
+    return conf
+
+
+def query_dice_sums(pred_logits, pred_masks, target, void_index: int = 0, label_offset: int = 1):
+    """Per sample and kept class c the three sums of _get_dice (maskformer_train_seg.py:287-302) over the pixels: p*t, p and t,
+    with p = query_semseg's score and t = (target - label_offset == c); masks resized to target's (H, W).  Returns (B,K,3)
+    float64 on the device; fixed summation order, bitwise reproducible.  Not differentiable; no host sync."""
+    with torch.no_grad():
+        if target.dim() != 3:
+            raise ValueError("query_dice_sums: a (B, H, W) target expected (got %s)" % (tuple(target.shape),))
+        lg, mk, dims, K = _query_args("query_dice_sums", pred_logits, pred_masks, target.shape[1:], void_index)
+        target = _query_target("query_dice_sums", target, dims[0])
+        B, K1, H, W = dims[0], dims[2], dims[5], dims[6]
+        sums = torch.zeros(B, K, 3, dtype=torch.float64, device=lg.device)
+        if target.numel():
+            n = _lib.lib().mmae_query_dice_ws_floats(B, K1, H, W)
+            if n < 0:
+                raise _lib.MmaeLibraryError("mmae_query_dice_ws_floats failed: invalid argument (MMAE_ERR_ARG)")
+            ws = torch.empty(n, dtype=torch.float32, device=lg.device)
+            call("mmae_query_dice", dt(lg), dt(mk), *dims, ptr(lg), ptr(mk), int(void_index), ptr(target), int(label_offset),
+                 ptr(ws), ptr(sums), stream())
+    return sums
+
+
 # ------------------------------------------------------------------------------------------------ mask bookkeeping
 def masks_from_draws(dirichlet, noise, noise_all, N: int):
     """dirichlet (R,M) f32, noise (R,M,P) f32, noise_all (R,M*P) f32 on device ->
