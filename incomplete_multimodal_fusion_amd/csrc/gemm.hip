@@ -41,42 +41,14 @@ namespace {
 __device__ __forceinline__ unsigned gm_pack2(float lo, float hi) {          // one v_cvt_pk_bf16_f32
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
 }
-// GELU of the FF1 + GEGLU epilogue (exact-erf GELU of the reference: F.gelu, DSI-MM/zorro_utils.py:115-118).  Three forms, chosen at build time:
-//   GM_GELU_FAST 1 (default since round 5): x * sigma(x (c0 + c1 x^2 + c2 x^4)), coefficients fitted (minimax on |x| <= 9, x^2 clamped there) to
-//     |gelu - x Phi(x)| <= 2.6e-5 for EVERY bf16 input: the product g = gelu(gate) * val is rounded to bf16 (relative 2^-9) right after, and the
-//     bf16-rounded gelu differs from the correctly rounded erf form for 18 of the 17 745 bf16 gates with |gelu| >= 0.02, by one ulp -- asserted
-//     ON THE DEVICE over all 65 280 finite gates by tests/test_gpu_gemm.py::test_gemm_geglu_epilogue_gelu_over_every_bf16_gate.  9 instructions
-//     / 11 issue slots per gate.  A documented deviation: the fastest form measured.
-//   GM_GELU_LUT 1 (round 6, `make EXTRA=-DGM_GELU_LUT=1`): x * Phi(x) with Phi LOOKED UP -- the gate the product is formed from is a bf16 value,
-//     i.e. one of 65 536 numbers; Phi of the 2 x 2048 of them with |x| in [2^-12, 16) sits in LDS as fp32 (16 KB behind the tile buffers,
-//     csrc/gelu_phi_table.inc from tools/gen_phi_table.py: erfc in double, rounded once), the index is clamped (|x| < 2^-12: 0.5 +- 1e-4;
-//     |x| >= 16: exactly 1 / 0).  EXACT: 0 of the 17 745 gates differ from the correctly rounded erf form.  6 integer instructions + one
-//     ds_read_b32 + one multiply per gate (8 slots) -- and SLOWER: the 64-address gathers cost the LDS more than the 3 slots save
-//     (epilogue 200.5 vs 190.6 us per launch at the FF1 shape, step 155.5 vs 154.9 ms, three alternations on one box).  Not the default.
-//   GM_GELU_FAST 0: x * Phi(x), Phi from one exp2 + one rcp (Abramowitz-Stegun 7.1.26, |err| <= 1.5e-7) -- the approximation of
-//     rowops.hip's geglu kernels (fp32 mode and the un-fused path); 13 instructions / 15 slots; +0.8 ms per step (round 5).
-#ifndef GM_GELU_LUT
-#define GM_GELU_LUT 0
-#endif
-#ifndef GM_GELU_FAST
-#define GM_GELU_FAST 1
-#endif
-#define GM_PHI_LDS 131072          // byte offset of the Phi table in LDS (EPI 1 only: 128 KB of tiles + 16 KB)
-#if GM_GELU_LUT
-__device__ const unsigned gm_phi_table[4096] = {
-#include "gelu_phi_table.inc"
-};
-// Phi of the bf16 value in bits [SH, SH + 16) of w
-template <int SH>
-__device__ __forceinline__ float gm_phi_lut(const char* lds, unsigned w) {
-    const int t = (int)__builtin_amdgcn_ubfe(w, SH, 15) - 0x3980;
-    const unsigned tc = (unsigned)min(max(t, 0), 2047);                      // one v_med3_i32
-    const unsigned idx = ((w >> (SH + 4)) & 0x800u) | tc;                 // sign bit -> bit 11: the negative half of the table
-    return *reinterpret_cast<const float*>(lds + GM_PHI_LDS + (idx << 2));
-}
-#endif
+// GELU of the FF1 + GEGLU epilogue (exact-erf GELU of the reference: F.gelu, DSI-MM/zorro_utils.py:115-118).  The two other forms that
+// were measured (Phi from an LDS table, Abramowitz-Stegun 7.1.26) are recorded in profiles/EXPERIMENTS.md.
+//   x * sigma(x (c0 + c1 x^2 + c2 x^4)), coefficients fitted (minimax on |x| <= 9, x^2 clamped there) to |gelu - x Phi(x)| <= 2.6e-5 for
+//   EVERY bf16 input: the product g = gelu(gate) * val is rounded to bf16 (relative 2^-9) right after, and the bf16-rounded gelu differs
+//   from the correctly rounded erf form for 18 of the 17 745 bf16 gates with |gelu| >= 0.02, by one ulp -- asserted ON THE DEVICE over all
+//   65 280 finite gates by tests/test_gpu_gemm.py::test_gemm_geglu_epilogue_gelu_over_every_bf16_gate.  9 instructions / 11 issue slots per
+//   gate.  A documented deviation: the fastest form measured.
 __device__ __forceinline__ float gm_gelu(float x) {
-#if GM_GELU_FAST
     // the polynomial is clamped through its argument x^2 (not x): beyond |x| = 9 the exponent x * p(81) keeps growing linearly, so the
     // factor goes to exactly 1 (x -> +big: g == x) and exactly 0 (x -> -big: g == -0; with x itself clamped a gate of -1e30 came out
     // as -2.3e18).  Same instruction count as the v_med3 form; identical results on |x| <= 9.
@@ -85,22 +57,8 @@ __device__ __forceinline__ float gm_gelu(float x) {
     const float p = fmaf(fmaf(1.01426305e-3f, x2, -1.06775723e-1f), x2, -2.30112136f);
     const float e = __builtin_amdgcn_exp2f(x * p);
     return x * __builtin_amdgcn_rcpf(1.f + e);
-#else
-    const float e = __builtin_amdgcn_exp2f(-0.72134752044448170f * x * x);
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.23164189f, fabsf(x), 1.f));
-    float poly = fmaf(0.5f * 1.061405429f, t, 0.5f * -1.453152027f);
-    poly = fmaf(poly, t, 0.5f * 1.421413741f);
-    poly = fmaf(poly, t, 0.5f * -0.284496736f);
-    poly = fmaf(poly, t, 0.5f * 0.254829592f);
-    const float half_erfc = poly * (t * e);
-    return fmaf(-fabsf(x), half_erfc, fmaxf(x, 0.f));
-#endif
 }
 
-#ifndef GM_EPI_DIAG
-#define GM_EPI_DIAG 0             // 1 / 2 / 3: timing-only builds of the GEGLU epilogue (no GELU / no product store / h in 8-byte stores) for
-                                  // tools/probes/geglu_epi_probe.py -- wrong results by construction
-#endif
 struct GemmArgs {
     const bf16* A; const bf16* W; bf16* C; bf16* G;      // G: GEGLU product (EPI 1), else unused
     int M, N, K;                                         // EPI 1: N = F output pairs (W has 2 F rows: val rows [0, F), gate rows [F, 2 F))
@@ -108,16 +66,14 @@ struct GemmArgs {
     int ntm, ntn;                                        // tiles: ceil(M / 256) x N / 256 (EPI 1: F / 128)
 };
 
-#ifndef GM_GN
-#define GM_GN 8                   // N-tiles of a chunk: the W panels an XCD keeps L2-resident while its A panels stream (A/B knob)
-#endif
 struct TileXY { int tm, tn; };
 // Tiles of one XCD group x (= workgroup % 8: the workgroups that share an L2 under round-robin placement -- speed only): M-panels
 // [m0, m1), walked in chunks of up to 8 N-tiles (a chunk's W panels stay L2-resident while the A panels stream); local tile index i.
 __device__ __forceinline__ TileXY tile_of(int x, int i, int ntm, int ntn) {
     const int q = ntm / 8, r = ntm % 8;
     const int m0 = x * q + (x < r ? x : r), rows = q + (x < r ? 1 : 0);
-    const int GN = ntn < GM_GN ? ntn : GM_GN, nc = ntn / GN, rem = ntn - nc * GN, full = nc * rows * GN;
+    constexpr int CHUNK = 8;          // N-tiles of a chunk: the W panels an XCD keeps L2-resident while its A panels stream
+    const int GN = ntn < CHUNK ? ntn : CHUNK, nc = ntn / GN, rem = ntn - nc * GN, full = nc * rows * GN;
     TileXY t;
     if (i < full) { const int c = i / (rows * GN), rr = i - c * rows * GN; t.tm = m0 + rr / GN; t.tn = c * GN + rr % GN; }
     else { const int rr = i - full; t.tm = m0 + rr / rem; t.tn = nc * GN + rr % rem; }
@@ -225,36 +181,23 @@ __device__ __forceinline__ void store_half(const f32x4 (&acc)[8][4], const Lane&
                 // round them; the product is formed from those rounded values (= what geglu_fwd_kernel computes from h)
                 const unsigned hv = gm_pack2(acc[mi][0][reg], acc[mi][1][reg]), hg = gm_pack2(acc[mi][2][reg], acc[mi][3][reg]);
                 const bf16x2 bv = __builtin_bit_cast(bf16x2, hv), bg = __builtin_bit_cast(bf16x2, hg);
-#if GM_EPI_DIAG == 1          // timing only: no GELU
-                const unsigned pr = gm_pack2((float)bg[0] * (float)bv[0], (float)bg[1] * (float)bv[1]);
-#elif GM_GELU_LUT
-                const unsigned pr = gm_pack2((float)bg[0] * gm_phi_lut<0>(L.lds, hg) * (float)bv[0], (float)bg[1] * gm_phi_lut<16>(L.lds, hg) * (float)bv[1]);
-#else
                 const unsigned pr = gm_pack2(gm_gelu((float)bg[0]) * (float)bv[0], gm_gelu((float)bg[1]) * (float)bv[1]);
-#endif
                 const int so = __builtin_amdgcn_readfirstlane(corigin + (16 * mi + reg) * L.ldc2);
-#if GM_EPI_DIAG == 3          // timing only: h as ONE 8-byte store per lane (val / gate pairs interleaved inside the tile's 256 columns)
-                __builtin_amdgcn_raw_buffer_store_b64(u32x2{hv, hg}, rsC, L.voffC, so, GM_STORE_AUX);
-#else
                 __builtin_amdgcn_raw_buffer_store_b32(hv, rsC, L.voffC, so, GM_STORE_AUX);
                 __builtin_amdgcn_raw_buffer_store_b32(hg, rsC, L.voffC, so + L.gate_off, GM_STORE_AUX);
-#endif
-#if GM_EPI_DIAG == 2          // timing only: the product is computed and kept live, its store dropped by a record count of 0
-                __builtin_amdgcn_raw_buffer_store_b32(pr, gm_rsrc(L.G, 0), L.voffG, __builtin_amdgcn_readfirstlane(gorigin + (16 * mi + reg) * L.ldg2), GM_STORE_AUX);
-#else
                 __builtin_amdgcn_raw_buffer_store_b32(pr, rsG, L.voffG, __builtin_amdgcn_readfirstlane(gorigin + (16 * mi + reg) * L.ldg2), GM_STORE_AUX);
-#endif
             }
         }
     }
 }
-#define GM_PHASE_TAIL(Q, FIRST)                                            \
+// The second half of every phase, here and in the TN kernel below; the argument is the phase's MFMA call (variadic: its template commas).
+#define GM_PHASE_TAIL(...)                                                 \
     __builtin_amdgcn_sched_barrier(0);                                     \
     __builtin_amdgcn_s_barrier();                                          \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                     \
     __builtin_amdgcn_sched_barrier(0);                                     \
     __builtin_amdgcn_s_setprio(1);                                         \
-    mfma_phase<Q, FIRST>(f, acc);                                          \
+    __VA_ARGS__;                                                           \
     __builtin_amdgcn_s_setprio(0);                                         \
     __builtin_amdgcn_sched_barrier(0);                                     \
     __builtin_amdgcn_s_barrier();                                          \
@@ -269,26 +212,26 @@ template <int EPI, int KIND>
 __device__ __forceinline__ void ktile(const Lane& L, const Ctx& c1, int kt1, const Ctx& c2, int kt2, int b, int wave, Frags& f, f32x4 (&acc)[8][4],
                                       const Out& prev, const Out& cur) {
     constexpr bool FIRST = KIND == 1, LAST = KIND == 3;
-    constexpr int SPP = EPI == 0 ? 8 : (GM_EPI_DIAG == 3 ? 16 : 24);
+    constexpr int SPP = EPI == 0 ? 8 : 24;
     load_frags<0>(L, b, f);
     stageW(L, c1, kt1, b ^ 1, 1, wave);
     if (FIRST) store_half<EPI, 1, 0>(acc, L, prev);
-    GM_PHASE_TAIL(0, FIRST)
+    GM_PHASE_TAIL(mfma_phase<0, FIRST>(f, acc))
     load_frags<1>(L, b, f);
     stageA(L, c1, kt1, b ^ 1, 1, wave);
     // A-hi of THIS K-tile (issued 4 staging steps ago) has landed
     if (FIRST) GM_VMCNT(vmc(8 + 3 * SPP)); else if (KIND == 2) GM_VMCNT(vmc(8 + SPP)); else GM_VMCNT(8);
     if (FIRST) store_half<EPI, 1, 1>(acc, L, prev);
-    GM_PHASE_TAIL(1, FIRST)
+    GM_PHASE_TAIL(mfma_phase<1, FIRST>(f, acc))
     load_frags<2>(L, b, f);
     stageA(L, c2, kt2, b, 0, wave);
     if (LAST) store_half<EPI, 0, 0>(acc, L, cur);
-    GM_PHASE_TAIL(2, FIRST)
+    GM_PHASE_TAIL(mfma_phase<2, FIRST>(f, acc))
     stageW(L, c2, kt2, b, 0, wave);
     // A-lo, W half 0, W half 1 of the next K-tile have landed
     if (LAST) GM_VMCNT(vmc(6 + SPP)); else if (FIRST) GM_VMCNT(vmc(6 + 2 * SPP)); else GM_VMCNT(6);
     if (LAST) store_half<EPI, 0, 1>(acc, L, cur);
-    GM_PHASE_TAIL(3, FIRST)
+    GM_PHASE_TAIL(mfma_phase<3, FIRST>(f, acc))
 }
 
 template <int EPI>
@@ -316,7 +259,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
         const int ra = (128 * wr + j) * 128 + 16 * (g ^ (j & 7));
         const int rw = 32768 + (64 * wc + j) * 128 + 16 * (g ^ (j & 7));
         L.rdA[0] = ra; L.rdA[1] = ra ^ 64; L.rdW[0] = rw; L.rdW[1] = rw ^ 64;
-        L.voffC = 4 * g * L.ldc2 + (EPI == 0 || GM_EPI_DIAG == 3 ? 8 : 4) * j;
+        L.voffC = 4 * g * L.ldc2 + (EPI == 0 ? 8 : 4) * j;
         L.voffG = 4 * g * L.ldg2 + 4 * j;
     }
     // this wave's pieces cover LDS rows 8 wave .. + 7 of a 64-row group = MFMA columns 8 (wave & 1) .. + 7 of n-tile wave >> 1
@@ -331,7 +274,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
     auto out_of = [&](TileXY t) {
         Out o;
         o.nC = szC; o.nG = szG;
-        o.c = (t.tm * 256 + 128 * wr) * L.ldc2 + (t.tn * (EPI == 0 || GM_EPI_DIAG == 3 ? 256 : 128) + (EPI == 0 || GM_EPI_DIAG == 3 ? 64 : 32) * wc) * 2;
+        o.c = (t.tm * 256 + 128 * wr) * L.ldc2 + (t.tn * (EPI == 0 ? 256 : 128) + (EPI == 0 ? 64 : 32) * wc) * 2;
         o.g = EPI == 0 ? 0 : (t.tm * 256 + 128 * wr) * L.ldg2 + (t.tn * 128 + 32 * wc) * 2;
         return o;
     };
@@ -341,12 +284,6 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
     TileXY cur = tile_of(x, jw, p.ntm, p.ntn);
     Ctx c, cn;
     origin(c, cur, true);
-#if GM_GELU_LUT
-    if (EPI == 1) {                                         // the Phi table: 16 pieces of 1 KiB, two per wave, OLDER than the tile pieces the vmcnt(6) below leaves in flight
-        gm_dma(gm_phi_table, 16384u, 16 * lane, 2048 * wave, lds + GM_PHI_LDS + 2048 * wave);
-        gm_dma(gm_phi_table, 16384u, 16 * lane, 2048 * wave + 1024, lds + GM_PHI_LDS + 2048 * wave + 1024);
-    }
-#endif
     stageA(L, c, 0, 0, 0, wave); stageW(L, c, 0, 0, 0, wave); stageW(L, c, 0, 0, 1, wave); stageA(L, c, 0, 0, 1, wave);
     stageA(L, c, 1, 1, 0, wave); stageW(L, c, 1, 1, 0, wave);
     GM_VMCNT(6);
@@ -402,7 +339,7 @@ bool gm_lds_opt_in(K kernel, int bytes, std::atomic<bool> (&done)[64]) {
 template <int EPI>
 int launch_gemm(const GemmArgs& a, hipStream_t st) {
     static std::atomic<bool> attr_set[64];
-    constexpr int ldsb = 131072 + ((EPI == 1 && GM_GELU_LUT) ? 16384 : 0);
+    constexpr int ldsb = 131072;                                          // two 64 KB tile buffers
     if (!gm_lds_opt_in(gemm8p_kernel<EPI>, ldsb, attr_set)) return MMAE_ERR_LAUNCH;
     const long tiles = (long)a.ntm * a.ntn;
     const int nper = tiles >= 256 ? 32 : (int)((tiles + 7) / 8);          // workgroups per XCD group; one workgroup per CU (128 KB of LDS)
@@ -530,17 +467,6 @@ __device__ __forceinline__ void tn_mfma(const TnFrags& f, f32x4 (&acc)[8][4]) {
         for (int tj = 0; tj < 4; ++tj)
             acc[4 * QA + ti][tj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[ti], f.b[tj], acc[4 * QA + ti][tj], 0, 0, 0);
 }
-#define TN_PHASE_TAIL(QA)                                                  \
-    __builtin_amdgcn_sched_barrier(0);                                     \
-    __builtin_amdgcn_s_barrier();                                          \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                     \
-    __builtin_amdgcn_sched_barrier(0);                                     \
-    __builtin_amdgcn_s_setprio(1);                                         \
-    tn_mfma<QA>(f, acc);                                                   \
-    __builtin_amdgcn_s_setprio(0);                                         \
-    __builtin_amdgcn_sched_barrier(0);                                     \
-    __builtin_amdgcn_s_barrier();                                          \
-    __builtin_amdgcn_sched_barrier(0);
 
 // K-tile t with t mod 5 == R: its steps 4 t .. 4 t + 3 sit in slots (4 R + j) mod 10; phase q issues step 4 t + q + 7 into slot (4 R + q + 7) mod 10
 // (kinds 3, 0, 1, 2 of K-tiles t+1, t+2, t+2, t+2).  Waits in phases 1 and 3: vmcnt(10) = five steps stay in flight.
@@ -549,18 +475,18 @@ __device__ __forceinline__ void tn_ktile(const TnLane& L, int t, int wave, TnFra
     constexpr int S0 = (4 * R) % 10, S1 = (4 * R + 1) % 10, S2 = (4 * R + 2) % 10, S3 = (4 * R + 3) % 10;
     tn_load<0, S0, S1>(L, f);
     tn_stage_step<3>(L, t + 1, (4 * R + 7) % 10, wave);
-    TN_PHASE_TAIL(0)
+    GM_PHASE_TAIL(tn_mfma<0>(f, acc))
     tn_load<1, S0, S1>(L, f);
     tn_stage_step<0>(L, t + 2, (4 * R + 8) % 10, wave);
     GM_VMCNT(10);
-    TN_PHASE_TAIL(1)
+    GM_PHASE_TAIL(tn_mfma<1>(f, acc))
     tn_load<0, S2, S3>(L, f);
     tn_stage_step<1>(L, t + 2, (4 * R + 9) % 10, wave);
-    TN_PHASE_TAIL(0)
+    GM_PHASE_TAIL(tn_mfma<0>(f, acc))
     tn_load<1, S2, S3>(L, f);
     tn_stage_step<2>(L, t + 2, (4 * R + 10) % 10, wave);
     GM_VMCNT(10);
-    TN_PHASE_TAIL(1)
+    GM_PHASE_TAIL(tn_mfma<1>(f, acc))
 }
 
 __global__ __launch_bounds__(512, 2) void gemm_tn8p_kernel(TnArgs p) {

@@ -1130,30 +1130,15 @@ def drop_path_row_scale(u: torch.Tensor, drop_prob: float, counts):
     s = torch.floor(keep + u.reshape(-1).float()) / keep
     return torch.cat([s.repeat_interleave(int(c)) for c in counts]).contiguous()
 
-FF_CHUNKS = 1      # see _FeedForwardGEGLU: 2 was measured, no net gain
 PAD_FF = True      # a GEGLU width that fits none of the own GEMM's tiles (ViT-L: 2730) runs on zero-padded operand copies (tools/tuning_env.py: MMAE_PAD_FF)
 PAD_FF_MIN_TILES = 128     # ... when FeedForward[3] has at least this many output tiles.  Lower than _OWN_GEMM_MIN_TILES: the alternative here is a
                            # library GEMM at an unaligned width (config 5, same-box A/B: 512 -> 128 is 153.2 -> 146.8 ms/step; no padding: 169.0)
 
 
-def _row_chunks(rows: int, n: int):
-    """n nearly equal row ranges with 256-aligned boundaries (GEMM tiles stay whole)."""
-    if rows < 8192 or n <= 1:
-        return [(0, rows)]
-    n = min(n, rows // 4096)
-    step = (rows + n - 1) // n
-    step = (step + 255) // 256 * 256
-    return [(a, min(rows, a + step)) for a in range(0, rows, step)]
-
-
 class _FeedForwardGEGLU(torch.autograd.Function):
-    """f = GEGLU(y @ W1^T) @ W2^T (FeedForward[1:4], zorro_utils.py:115-128) as ONE node, optionally evaluated in
-    FF_CHUNKS row chunks (GEMM1 -> GEGLU -> GEMM2 back to back per chunk, so the (rows, 2*ffi) intermediate -- 1.3 GB at
-    the bench batch -- is consumed while its tail still sits in the 256 MB Infinity Cache).  Measured: in isolation
-    GEGLU drops 475 -> 359 us with two chunks (tools/probes/mall_chunk_probe.py); inside the step GEGLU gains 1.2 ms and
-    the half-size GEMMs lose 1.2 ms, so the default stays at one chunk.  The backward walks the same chunks:
-    dg = df @ W2 -> GEGLU' -> dy = dh @ W1; the two weight gradients are split-K GEMMs over all rows afterwards.
-    Both weights must be used once per step (see linear())."""
+    """f = GEGLU(y @ W1^T) @ W2^T (FeedForward[1:4], zorro_utils.py:115-128) as ONE node: GEMM1 (+ GEGLU in its epilogue where the own
+    kernel takes the shape) -> GEMM2.  The backward is dg = df @ W2 -> GEGLU' -> dy = dh @ W1, then the two weight gradients as
+    split-K GEMMs over all rows.  Both weights must be used once per step (see linear())."""
 
     @staticmethod
     def forward(ctx, y, w1, w2):
@@ -1197,13 +1182,12 @@ class _FeedForwardGEGLU(torch.autograd.Function):
         g = torch.empty(rows, F, dtype=T, device=y.device)
         f = torch.empty(rows, w2.shape[0], dtype=T, device=y.device)
         with _NoAutocast():
-            for a, b in _row_chunks(rows, FF_CHUNKS):
-                if own_geglu_ok(y[a:b], w1c, h[a:b], g[a:b]):
-                    gemm_geglu(y[a:b], w1c, h[a:b], g[a:b])         # FeedForward[1] + GEGLU in one kernel (csrc/gemm.hip)
-                else:
-                    matmul_nt(y[a:b], w1c, out=h[a:b])
-                    call("mmae_geglu_fwd", dt(T), b - a, F, ptr(h[a:b]), ptr(g[a:b]), stream())
-                matmul_nt(g[a:b], w2c, out=f[a:b])
+            if own_geglu_ok(y, w1c, h, g):
+                gemm_geglu(y, w1c, h, g)                             # FeedForward[1] + GEGLU in one kernel (csrc/gemm.hip)
+            else:
+                matmul_nt(y, w1c, out=h)
+                call("mmae_geglu_fwd", dt(T), rows, F, ptr(h), ptr(g), stream())
+            matmul_nt(g, w2c, out=f)
         ctx.save_for_backward(y, h, g, w1c, w2c)
         ctx.cfg = (w1, w2, gv1, gv2, None)
         return f
@@ -1238,13 +1222,11 @@ class _FeedForwardGEGLU(torch.autograd.Function):
         dh = torch.empty_like(h)
         dy = torch.empty_like(y) if ctx.needs_input_grad[0] else None
         with _NoAutocast():
-            chunks = _row_chunks(rows, FF_CHUNKS)
-            dg = torch.empty(max(b - a for a, b in chunks), F, dtype=T, device=y.device)
-            for a, b in chunks:
-                matmul_nt(df[a:b], w2t, out=dg[:b - a])                   # dg = df @ W2
-                call("mmae_geglu_bwd", dt(T), b - a, F, ptr(h[a:b]), ptr(dg), ptr(dh[a:b]), stream())
-                if dy is not None:
-                    matmul_nt(dh[a:b], w1t, out=dy[a:b])                  # dy = dh @ W1
+            dg = torch.empty(rows, F, dtype=T, device=y.device)
+            matmul_nt(df, w2t, out=dg)                                    # dg = df @ W2
+            call("mmae_geglu_bwd", dt(T), rows, F, ptr(h), ptr(dg), ptr(dh), stream())
+            if dy is not None:
+                matmul_nt(dh, w1t, out=dy)                                # dy = dh @ W1
             both = gv1 is not None and gv2 is not None
             gw2 = _wgrad(df, g, gv2, (w2,) if both else None)
             gw1 = _wgrad(dh, y, gv1, (w1,) if both else None)

@@ -137,7 +137,7 @@ def test_gemm_geglu_matches_separate_path(M, F, K):
 
 
 def test_gemm_geglu_epilogue_gelu_over_every_bf16_gate():
-    """The FF1 + GEGLU epilogue's GELU (csrc/gemm.hip gm_gelu, GM_GELU_FAST 1: x * sigma(x (c0 + c1 x^2 + c2 x^4)), a documented
+    """The FF1 + GEGLU epilogue's GELU (csrc/gemm.hip gm_gelu, the fitted-sigmoid form: x * sigma(x (c0 + c1 x^2 + c2 x^4)), a documented
     deviation from the reference's erf GELU, DSI-MM/zorro_utils.py:115-118) evaluated ON THE DEVICE for EVERY finite bf16 gate: row m
     of A carries bf16 bit pattern m in column 0 and 1.0 in column 1, the gate rows of W1 pick column 0, the val rows column 1 -- so
     the accumulator of (m, gate) is exactly that bf16 value, val is exactly 1 and the stored product is bf16(gelu(gate)).
@@ -257,11 +257,13 @@ def test_padded_ff_shadows_match_the_weights(D, F):
     check()
 
 
-@pytest.mark.parametrize("rows,D,F", [(4096, 512, 300), (6000, 1024, 2730)])
-def test_feedforward_geglu_padded_own_gemm_vs_fp64_and_library_path(rows, D, F, monkeypatch):
-    """ops.feedforward_geglu at a GEGLU width that fits none of the own GEMM's tiles: the padded path (gemm8p on the engine's padded
-    copies; asserted engaged) against the fp64 composition of zorro_utils.py:115-128 and against the library path at the exact width --
-    output, input gradient and both weight gradients (written in place into the flat buffer at the EXACT shapes)."""
+@pytest.mark.parametrize("rows,D,F", [(4096, 512, 300), (6000, 1024, 2730), (8229, 512, 512)])
+def test_feedforward_geglu_own_gemm_padded_and_unpadded_vs_fp64_and_library_path(rows, D, F, monkeypatch):
+    """ops.feedforward_geglu on the own kernels (gemm8p; asserted engaged) against the fp64 composition of zorro_utils.py:115-128 and
+    against the library path at the exact width -- output, input gradient and both weight gradients (written in place into the flat
+    buffer at the EXACT shapes).  F = 300 / 2730 fit none of the own GEMM's tiles: the padded path, on the engine's padded copies.
+    F = 512 needs no padding: the unpadded branch (the ViT-B product path) through the autograd node, every projection inside the own
+    kernel's shape rules (N % 256 == 0, 128 GEGLU pairs; K >= 384, K % 128 == 0), 8229 rows ending in a partial M-tile."""
     from incomplete_multimodal_fusion_amd import ops
     w1, w2, eng = _ff_engine(D, F, 1)
     y = (torch.randn(rows, D, device=DEV) * 0.7).to(torch.bfloat16).requires_grad_(True)

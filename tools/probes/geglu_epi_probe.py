@@ -1,10 +1,9 @@
 #!/usr/bin/env python
 """Where the FF1 + GEGLU epilogue of the own GEMM (csrc/gemm.hip, gemm8p_kernel<1>) spends its time: the same shapes timed with the
-library given by MMAE_HIP_LIB (product, the previous epilogue, or a timing-only build: `-DGM_EPI_DIAG=1` no GELU, `=2` no product store,
-`=3` h written with 8-byte stores), next to the plain N = 2 F GEMM of the same kernel family (EPI 0: the epilogue-free reference).
-One process per library (the library is bound at import); run them alternately:
+library given by MMAE_HIP_LIB (the product library, or one built from another commit), next to the plain N = 2 F GEMM of the same
+kernel family (EPI 0: the epilogue-free reference).  One process per library (the library is bound at import); run them alternately:
 
-    for l in "" prev d1 d2 d3; do MMAE_HIP_LIB=${l:+tools/probes/libmmae_epi_$l.so} python tools/probes/geglu_epi_probe.py; done
+    for l in "" prev; do MMAE_HIP_LIB=${l:+tools/probes/libmmae_epi_$l.so} python tools/probes/geglu_epi_probe.py; done
 
 With --dump the fusion-rows h / g go to gpurun_out/epi_<library>.pt (bitwise comparison of two builds on the same inputs)."""
 import os

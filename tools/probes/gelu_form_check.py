@@ -1,4 +1,4 @@
-"""CPU check (numpy, float32 emulation) of the GELU form of the FF1 + GEGLU GEMM epilogue (csrc/gemm.hip gm_gelu, GM_GELU_FAST 1):
+"""CPU check (numpy, float32 emulation) of the GELU form of the FF1 + GEGLU GEMM epilogue (csrc/gemm.hip gm_gelu, the fitted-sigmoid form):
 x * sigma(x (c0 + c1 x^2 + c2 x^4)) with the argument clamped to |x| <= 9, against the exact x Phi(x) over EVERY bf16 input --
 the epilogue's inputs are bf16 values of h -- and after rounding both to bf16.   python tools/probes/gelu_form_check.py [--fit]"""
 import sys

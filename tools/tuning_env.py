@@ -7,7 +7,7 @@ The product package reads NO tuning variable itself (only MMAE_HIP_LIB, the libr
     MMAE_FUSED_CAST      multimae_crossattn.FUSED_FINAL_CAST
     MMAE_FUSED_CTX       multimae_crossattn.FUSED_DECODER_CTX
     MMAE_DUAL_LN         multimae_crossattn.DUAL_LAYERNORM
-    MMAE_SPLITK_CAP / MMAE_SPLITK_MAX / MMAE_WGRAD_PRIO / MMAE_FF_CHUNKS      the ops.py constants of the same names
+    MMAE_SPLITK_CAP / MMAE_SPLITK_MAX / MMAE_WGRAD_PRIO      the ops.py constants of the same names
     MMAE_OWN_GEMM        ops.OWN_GEMM               bit 0: own 8-phase GEMM for forward / input-gradient projections, bit 1: for weight gradients
     MMAE_ASYNC_DRAW      multimae_crossattn.ASYNC_DRAW_COPY   0: the mask draw's host->device copy from pageable memory (one host/GPU sync per step)
     MMAE_DEFER_SPLITK    ops.DEFER_SPLITK           0: one split-K sum launch per weight gradient instead of one per layer
@@ -34,7 +34,6 @@ def apply(verbose=True):
     put(ops, "_SPLITK_CAP", "MMAE_SPLITK_CAP", int)
     put(ops, "_SPLITK_MAX", "MMAE_SPLITK_MAX", int)
     put(ops, "WGRAD_STREAM_PRIORITY", "MMAE_WGRAD_PRIO", int)
-    put(ops, "FF_CHUNKS", "MMAE_FF_CHUNKS", int)
     put(ops, "OWN_GEMM", "MMAE_OWN_GEMM", int)
     put(ops, "DEFER_SPLITK", "MMAE_DEFER_SPLITK", flag)
     put(ops, "PAD_FF", "MMAE_PAD_FF", flag)
